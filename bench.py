@@ -28,6 +28,11 @@ value = pairs of all ranks / max-over-ranks time.  `--shard` runs the same route
 "gather" is the send buffer itself); `--replicas` is the other multi-GPU shape (configs[4]: every rank its own
 scene, results all-gathered).
 
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs DIR (the last timed step's outputs) and prints the
+result line.  `--full` adds what else the bench measures: per-kernel profile events in the timed steps (kernel_ms_per_step,
+roofline, candidate_evals), parity against the reference's fixtures, and after the timed steps the serial re-timing, the drop-in
+block and the CPU baseline.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -559,6 +564,39 @@ class Sharded:
         return prev
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: what the last timed step returned, one float32 .npy per array — icp_poses (one row of 16 per ICP problem, the
+    pose's 16 floats as the library returns them), icp_errors, scores, labels (the int8 class ids as floats), min_dists; the further
+    scan pairs of --timesteps T as <name>_pair<k>.  Over DUMP_BYTES in all, the per-point arrays keep a fixed, seeded sample of their
+    rows (the same rows in each, listed in sample_rows.npy).  Written outside the timed region."""
+    arrays = {}
+    for k, o in enumerate(outs):
+        if o is None:
+            continue
+        sfx = "_pair%d" % k if k else ""
+        arrays["icp_poses" + sfx] = np.asarray(o["Ts"] if o.get("Ts") is not None else o["T"], np.float32).reshape(-1, 16)
+        arrays["icp_errors" + sfx] = np.asarray(o["errs"] if o.get("errs") is not None else o["err"], np.float32).reshape(-1)
+        arrays["scores" + sfx] = np.asarray(o["scores"], np.float32).reshape(-1)
+        arrays["labels" + sfx] = np.asarray(o["labels"]).astype(np.float32).reshape(-1)
+        arrays["min_dists" + sfx] = np.asarray(o["min_dists"], np.float32).reshape(-1)
+    per_point = [n for n in arrays if n.startswith(("labels", "min_dists"))]
+    small = sum(a.nbytes for n, a in arrays.items() if n not in per_point)
+    big = sum(arrays[n].nbytes for n in per_point)
+    if small + big > DUMP_BYTES:
+        n_rows = min(len(arrays[n]) for n in per_point)
+        keep = min(n_rows, (DUMP_BYTES - small - 4096 * (len(arrays) + 1)) // (4 * len(per_point) + 8))   # (float32 per array, float64 index)
+        rows = np.sort(np.random.default_rng(0).choice(n_rows, keep, replace=False))
+        for n in per_point:
+            arrays[n] = arrays[n][rows]
+        arrays["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(path, n + ".npy"), a)
+
+
 def parity_block(out, n_points, seed, knn, units, strong=False, centre=False, t0=0):
     """Distance of the LAST step's outputs from tests/golden/bench_seed11.npz — what the compiled reference computes for
     the same inputs (oracle/gen_golden_bench.py: pose / error after the 10 fixed iterations composed from the reference's
@@ -826,8 +864,15 @@ def main():
     ap.add_argument("--points", type=int, default=1_000_000, help="points per scan")
     ap.add_argument("--knn", choices=["hash", "brute"], default="hash",
                     help="candidate layout: LDS spatial-hash cells (default) or one brute tile")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the warm-up and the timed steps: no serial re-timing, no drop-in block afterwards (profiling runs: "
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel profile events in the timed steps (kernel_ms_per_step, roofline, candidate_evals), "
+                         "parity against the reference's fixtures, the serial re-timing, the drop-in block and the CPU baseline.  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (ICP poses and errors, scores, labels, min_dists) "
+                         "as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: only the warm-up and the timed steps, no serial re-timing, no drop-in block afterwards (profiling runs: "
                     "every kernel the process launches after its clouds are built then belongs to a step; RS_BENCH_MARK=1 starts each step with the "
                     "library's marker kernel)")
     ap.add_argument("--serial", action="store_true", help="issue the three consumers one after another")
@@ -846,6 +891,8 @@ def main():
     ap.add_argument("--launch-dry-run", action="store_true",
                     help="--gpus N > 1 without a launcher: print the N ranks' command and environment as JSON instead of starting them")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` as the driver may type it: this process becomes the launcher — it has not touched the GPU (no
@@ -972,8 +1019,10 @@ def main():
     drain()
     for x in (SH or []):
         x.reset_stats()
-    capi.profile_enable(True)
-    capi.profile_reset()
+    if args.full:
+        # (the profile's events and candidate counters ride in the timed steps: --full only)
+        capi.profile_enable(True)
+        capi.profile_reset()
     import gc
     gc.collect(); gc.disable()                  # no collector pauses inside the timed region
     barrier()
@@ -1013,39 +1062,14 @@ def main():
         elapsed = float(t.item())
 
     if rank == 0:
-        if sh is not None:
-            errs, Ts, its, scores, labels, mind = last
-            out = dict(err=errs[0], T=Ts[0], scores=scores, labels=labels, min_dists=mind, Ts=Ts, errs=errs)
-        else:
-            out = last
-        prof = {k: capi.profile_read(k) for k in ("nn_icp", "icp_moments", "nn_score", "nn_label")}
-        per_step = {k: v[1] / max(1, v[0]) * (ICP_ITERS if k in ("nn_icp", "icp_moments") else 1) * n_pairs for k, v in prof.items()}
-        shares = cu_shares() if conc else {}
-        mean = lambda f: float(np.mean([f(wk) for wk in W]))
-        # algorithmic bytes per launch (SURVEY.md §8d / BASELINE.md §3.5; DESIGN.md §6).  The label pass is ONE fused launch over all
-        # placements: a scene point (24 B) is read once, not once per placement — 24 + n_placements x 22 B per point.
-        alg_bytes = {"nn_icp": mean(lambda x: x["n_scan1"] * 56 + x["n_scan0"] * 16),
-                     "nn_score": mean(lambda x: N_POSES * x["n_obj"] * 40 + x["n_scan1"] * 16),
-                     "nn_label": mean(lambda x: x["n_scan1"] * (24 + N_PLACEMENTS * 22) + sum(len(p["np"][0]) for p in x["plc"][:N_PLACEMENTS]) * 16),
-                     "icp_moments": mean(lambda x: x["n_scan1"] * 56)}
-        by_kernel = {}
-        for k, (n_k, ms_k) in prof.items():
-            avg = (ms_k / max(1, n_k)) * 1e-3
-            tr, _ = read_traffic(k)
-            by_kernel[k] = {"avg_launch_ms": avg * 1e3, "launches": n_k, "alg_bytes_per_launch": alg_bytes[k], "cu_share": shares.get(k, 1.0),
-                            "achieved_GBs": alg_bytes[k] / avg / 1e9 if avg > 0 else 0.0, "frac": (alg_bytes[k] / avg / 1e9 / HBM_PEAK_GBS) if avg > 0 else 0.0,
-                            # HBM-side bytes per launch by the PMC counters (profiles/pmc_traffic.json, same kernel sources only) and the
-                            # fraction of the HBM peak those bytes make of this run's launch time
-                            "traffic": tr, "traffic_frac": (tr / avg / 1e9 / HBM_PEAK_GBS) if (tr and avg > 0) else None}
-        # roofline.kernel: the domain with the LONGEST time per step (the top row of a rocprofv3 --stats summary of this command).
-        # Round 4 reported the domain with the largest time x CU share instead; the rule now is fixed: longest interval.
-        dom = max(per_step, key=lambda k: per_step[k])
-        worst = min((k for k in by_kernel if by_kernel[k]["frac"] > 0), key=lambda k: by_kernel[k]["frac"], default=dom)
-        n_l, ms = prof[dom]
-        bytes_launch = alg_bytes[dom]
-        avg_s = (ms / max(1, n_l)) * 1e-3
-        achieved = bytes_launch / avg_s / 1e9 if avg_s > 0 else 0.0
-        traffic, traffic_note = read_traffic(dom)
+        def as_out(x):
+            if x is None or SH is None:
+                return x
+            errs, Ts, its, scores, labels, mind = x
+            return dict(err=errs[0], T=Ts[0], scores=scores, labels=labels, min_dists=mind, Ts=Ts, errs=errs)
+        out = as_out(last)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, [out] + [as_out(last_of.get(k)) for k in range(1, n_pairs)])
         if strong:
             wl = ("configs[3], strong scaling: ONE FIXED scene (~1M-pt scans) replicated per rank, its units sharded over the ranks: " + str(n_strong) + " ICP-NN problems "
                   "(each placement's ~50k-pt model -> scan, 0.075 / 50 deg, 10 it: lib/rs/rs_database.h:220-230), score-NN 256 poses x 10k, label-NN 8 placements; "
@@ -1077,6 +1101,43 @@ def main():
                                     % (sh.lay.words * 4 / 1e6, sh.t_gather / max(1, sh.n_exchanges) * 1e3, sh.t_fold / max(1, sh.n_exchanges) * 1e3,
                                        sh.t_compute / max(1, sh.step_index - sh.stat_from) * 1e3, sh.t_wait / max(1, sh.step_index - sh.stat_from) * 1e3)) if sharded
                                    else ("one fused all_gather(poses, scores, label partials) per step, overlapped with the next step" if dist is not None else "none")},
+            "icp_chains_gave_up_calls": int(capi.icp_chains_gave_up()),     # calls whose centroid chains gave a problem up and were run again by the replay (0 on scenes in one octant)
+            "ms_per_step_spread": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
+                                   "steps_over_1.3x_median": int((step_ms > 1.3 * np.median(step_ms)).sum())},
+            # the container's CPU cgroup around the timed region: a throttled period stalls every host thread of the process
+            "host": ({"cpu_max": cpu_before[0], "throttled_periods_in_timed_region": cpu_after[1] - cpu_before[1],
+                      "throttled_usec_in_timed_region": cpu_after[2] - cpu_before[2]} if cpu_before and cpu_after else None),
+        }
+    if rank == 0 and args.full:
+        prof = {k: capi.profile_read(k) for k in ("nn_icp", "icp_moments", "nn_score", "nn_label")}
+        per_step = {k: v[1] / max(1, v[0]) * (ICP_ITERS if k in ("nn_icp", "icp_moments") else 1) * n_pairs for k, v in prof.items()}
+        shares = cu_shares() if conc else {}
+        mean = lambda f: float(np.mean([f(wk) for wk in W]))
+        # algorithmic bytes per launch (SURVEY.md §8d / BASELINE.md §3.5; DESIGN.md §6).  The label pass is ONE fused launch over all
+        # placements: a scene point (24 B) is read once, not once per placement — 24 + n_placements x 22 B per point.
+        alg_bytes = {"nn_icp": mean(lambda x: x["n_scan1"] * 56 + x["n_scan0"] * 16),
+                     "nn_score": mean(lambda x: N_POSES * x["n_obj"] * 40 + x["n_scan1"] * 16),
+                     "nn_label": mean(lambda x: x["n_scan1"] * (24 + N_PLACEMENTS * 22) + sum(len(p["np"][0]) for p in x["plc"][:N_PLACEMENTS]) * 16),
+                     "icp_moments": mean(lambda x: x["n_scan1"] * 56)}
+        by_kernel = {}
+        for k, (n_k, ms_k) in prof.items():
+            avg = (ms_k / max(1, n_k)) * 1e-3
+            tr, _ = read_traffic(k)
+            by_kernel[k] = {"avg_launch_ms": avg * 1e3, "launches": n_k, "alg_bytes_per_launch": alg_bytes[k], "cu_share": shares.get(k, 1.0),
+                            "achieved_GBs": alg_bytes[k] / avg / 1e9 if avg > 0 else 0.0, "frac": (alg_bytes[k] / avg / 1e9 / HBM_PEAK_GBS) if avg > 0 else 0.0,
+                            # HBM-side bytes per launch by the PMC counters (profiles/pmc_traffic.json, same kernel sources only) and the
+                            # fraction of the HBM peak those bytes make of this run's launch time
+                            "traffic": tr, "traffic_frac": (tr / avg / 1e9 / HBM_PEAK_GBS) if (tr and avg > 0) else None}
+        # roofline.kernel: the domain with the LONGEST time per step (the top row of a rocprofv3 --stats summary of this command).
+        # Round 4 reported the domain with the largest time x CU share instead; the rule now is fixed: longest interval.
+        dom = max(per_step, key=lambda k: per_step[k])
+        worst = min((k for k in by_kernel if by_kernel[k]["frac"] > 0), key=lambda k: by_kernel[k]["frac"], default=dom)
+        n_l, ms = prof[dom]
+        bytes_launch = alg_bytes[dom]
+        avg_s = (ms / max(1, n_l)) * 1e-3
+        achieved = bytes_launch / avg_s / 1e9 if avg_s > 0 else 0.0
+        traffic, traffic_note = read_traffic(dom)
+        line.update({
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
                          "avg_launch_ms": ms / max(1, n_l), "launches": n_l, "alg_bytes_per_launch": bytes_launch,
@@ -1089,22 +1150,11 @@ def main():
                          "furthest_below_roofline": {"kernel": worst, "frac": by_kernel[worst]["frac"], "instructions_per_launch": read_instructions(worst)}},
             "roofline_by_kernel": by_kernel,
             "parity": parity_block(out, args.points, seed, args.knn, units, strong, centre=args.centre) if not sim_world else "not compared: RS_BENCH_SIM_WORLD runs one rank's share without the exchange",
-            "icp_chains_gave_up_calls": int(capi.icp_chains_gave_up()),     # calls whose centroid chains gave a problem up and were run again by the replay (0 on scenes in one octant)
-            "ms_per_step_spread": {"min": float(step_ms.min()), "median": float(np.median(step_ms)), "max": float(step_ms.max()),
-                                   "steps_over_1.3x_median": int((step_ms > 1.3 * np.median(step_ms)).sum())},
-            # the container's CPU cgroup around the timed region: a throttled period stalls every host thread of the process
-            "host": ({"cpu_max": cpu_before[0], "throttled_periods_in_timed_region": cpu_after[1] - cpu_before[1],
-                      "throttled_usec_in_timed_region": cpu_after[2] - cpu_before[2]} if cpu_before and cpu_after else None),
             # per-launch averages x launches per step (the ICP loop's events are sampled: one call in RS_HIP_PROF_EVERY)
             "kernel_ms_per_step": per_step,
             "profile_sampling": "ICP chain: events on every %s-th call (%d launches timed); score / label: every call" % (os.environ.get("RS_HIP_PROF_EVERY", "1"), n_l),
-        }
+        })
         if n_pairs > 1:      # the further scan pairs against their own reference fixtures
-            def as_out(x):
-                if x is None or SH is None:
-                    return x
-                errs, Ts, its, scores, labels, mind = x
-                return dict(err=errs[0], T=Ts[0], scores=scores, labels=labels, min_dists=mind, Ts=Ts, errs=errs)
             line["parity_pairs"] = [parity_block(as_out(last_of.get(k)), args.points, seed, args.knn, units, strong, centre=args.centre, t0=k) for k in range(1, n_pairs)]
         # "the real limiter is candidate evaluation ... so also report candidate-evals/s"
         # (candidates staged in LDS x the 64 query lanes that test each of them)
@@ -1135,6 +1185,7 @@ def main():
             except Exception as e:  # the baseline is reported, never required for the GPU number
                 line["cpu_baseline"] = {"value": None, "unit": "point-pairs/s", "cores": 0, "kind": "reference",
                                         "sample": f"unavailable: {e}"}
+    if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())
     if dist is not None:

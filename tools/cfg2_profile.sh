@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 export TMPDIR=/tmp; cd "$ROOT"; mkdir -p gpurun_out
 pts=${1:-1000000}
 for knn in hash brute; do
-  args="--steps 2 --warmup 1 --no-cpu-baseline --serial --knn $knn --points $pts"
+  args="--full --steps 2 --warmup 1 --no-cpu-baseline --serial --knn $knn --points $pts"
   python bench.py $args > gpurun_out/cfg2_${knn}_${pts}.json 2> gpurun_out/cfg2_${knn}_${pts}.err
   rm -rf gpurun_out/cfg2_stats_$knn
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/cfg2_stats_$knn -- python bench.py $args > /dev/null 2> gpurun_out/cfg2_stats_$knn.err

@@ -7,8 +7,8 @@
 set -e
 cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 R=gpurun_out/r06; mkdir -p $R profiles
-python bench.py > $R/bench_final.json 2> $R/bench_final.err
-python bench.py --serial --no-cpu-baseline > $R/bench_serial.json 2>> $R/bench_final.err
+python bench.py --full > $R/bench_final.json 2> $R/bench_final.err
+python bench.py --full --serial --no-cpu-baseline > $R/bench_serial.json 2>> $R/bench_final.err
 bash tools/profile.sh stats > $R/stats_head.txt 2>&1
 cp "$(find gpurun_out/prof_stats -name '*kernel_stats.csv' | head -1)" $R/kernel_stats_bench.csv
 cp gpurun_out/prof_stats_bench.json $R/bench_under_rocprof.json
@@ -19,7 +19,7 @@ bash tools/profile.sh traffic > $R/pmc_traffic_per_kernel.txt 2>&1
 python tools/pmc_summary.py --fold-domains > $R/pmc_fold_domains.txt 2>&1
 cp profiles/pmc_traffic.json $R/pmc_traffic.json; cp profiles/pmc_instructions.json $R/pmc_instructions.json
 bash tools/profile.sh trace > /dev/null 2>&1; cp gpurun_out/trace_last_step.txt $R/trace_one_serial_step.txt
-bash tools/profile.sh trace_dropin > /dev/null 2>&1; cp gpurun_out/trace_dropin_calls.txt $R/trace_dropin_calls.txt
+OUT=$R bash tools/profile.sh trace_dropin > /dev/null 2>&1      # (-> $R/trace_dropin_calls.txt)
 bash tools/score_scene_profile.sh > /dev/null 2>&1; cp gpurun_out/sq_profile.txt $R/score_scene_profile.txt
-python bench.py > $R/bench_final2.json 2>> $R/bench_final.err
+python bench.py --full > $R/bench_final2.json 2>> $R/bench_final.err
 cat $R/pmc_fold_domains.txt; tail -3 $R/trace_one_serial_step.txt; tail -c 600 $R/bench_final2.json

@@ -31,10 +31,10 @@ trace)   # per-dispatch timeline of ONE serial step of the timed workload, whole
   rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_trace -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --serial > /dev/null 2> gpurun_out/prof_trace.err
   python tools/pmc_summary.py --trace "$(find gpurun_out/prof_trace -name '*kernel_trace.csv' | head -1)" gpurun_out/trace_last_step.txt ;;
 trace_dropin)   # the same three consumers through librescan_dropin.so (host arrays in, results out): first call and a repeated one, kernel by kernel
-  rm -rf gpurun_out/prof_trace_dropin
+  OUT=${OUT:-bench_out}; mkdir -p "$OUT"; rm -rf "$OUT/prof_trace_dropin"     # (OUT=<dir>: where this mode's files go)
   export RS_HIP_PROF_EVERY=1000 RS_BENCH_MARK=1      # unit 0: the one timed (serial) step; units 1..4: the drop-in block's first call and its three repeated ones
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_trace_dropin -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --serial > gpurun_out/prof_trace_dropin.log 2> gpurun_out/prof_trace_dropin.err
-  python tools/pmc_summary.py --trace "$(find gpurun_out/prof_trace_dropin -name '*kernel_trace.csv' | head -1)" gpurun_out/trace_dropin_calls.txt all ;;
+  rocprofv3 --kernel-trace --output-format csv -d "$OUT/prof_trace_dropin" -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --serial > "$OUT/prof_trace_dropin.log" 2> "$OUT/prof_trace_dropin.err"
+  python tools/pmc_summary.py --trace "$(find "$OUT/prof_trace_dropin" -name '*kernel_trace.csv' | head -1)" "$OUT/trace_dropin_calls.txt" all ;;
 stats_serial)
   rm -rf gpurun_out/prof_stats_serial
   rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_stats_serial -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --serial > gpurun_out/prof_stats_serial_bench.json 2> gpurun_out/prof_stats_serial.err
