@@ -96,6 +96,36 @@ int rs_hip_radius_search( const rs_hip_cloud_t* target, const float* query, int6
                           float* distances_sq, int32_t* indices, size_t* n_neighbors,
                           uint64_t* total );
 
+/* ---- k-nearest search on the reference's own grid ------------------------------------ */
+
+/* msh_hash_grid_knn_search (lib/msh/msh_hash_grid.h:1291-1447), which is NOT an exact k-nearest
+ * search: it walks the bins of a grid whose geometry comes from the init radius (the points' box
+ * grown by 1e-4; cell = 2 radius, or max_dim / (32 sqrt 3) when radius <= 0; :413-449), shell by
+ * shell around the query's bin, skips a bin beyond the k-th distance held after the previous shell
+ * and stops one shell after k points are held.  A knn grid is that geometry over a device cloud's
+ * points (built on the device; the cloud may be destroyed afterwards).  dim = 2: a cloud of
+ * msh_hash_grid_init_2d points, (x, y, 0); its queries carry z = 0.  NULL on failure
+ * (rs_hip_last_error(); a radius so small against the box that the grid would need more than 2^26
+ * bins is refused rather than allocated). */
+#define RS_HIP_KNN_MAX_K 64      /* k cap of rs_hip_knn_search (one 64-lane wave holds a query's rows) */
+typedef struct rs_hip_knn_grid rs_hip_knn_grid_t;
+rs_hip_knn_grid_t* rs_hip_knn_grid_create( const rs_hip_cloud_t* cloud, float radius, int32_t dim );
+void               rs_hip_knn_grid_destroy( rs_hip_knn_grid_t* grid );
+/* the grid's bins per axis (w, h, d), cell edge and origin (min_pt: the grown box's corner); cell / min_pt may be NULL */
+int                rs_hip_knn_grid_geometry( const rs_hip_knn_grid_t* grid, int64_t dims[3], double* cell, float min_pt[3] );
+/* The same geometry computed on the host from n AoS points (no device needed); RS_HIP_E_CAPACITY
+ * where rs_hip_knn_grid_create would refuse the grid. */
+int                rs_hip_knn_geometry( const float* pos, int64_t n, float radius, int32_t dim,
+                                        int64_t dims[3], double* cell, float min_pt[3] );
+/* For every query (3 floats; host pointers in and out, any n_query) the reference's rows: row i
+ * holds n_neighbors[i] = min(k, points in the bins visited) entries, ascending in (dist², index),
+ * at distances_sq / indices + i*k; entries past n_neighbors[i] are left untouched.  Where the
+ * reference is undefined (a shell of more than 128 bins, fewer than k points, a query outside the
+ * box) the walk has no bin cap and ends once every bin has been visited.  k <= RS_HIP_KNN_MAX_K,
+ * else RS_HIP_E_CAPACITY.  n_neighbors and total may be NULL. */
+int rs_hip_knn_search( const rs_hip_knn_grid_t* grid, const float* query, int64_t n_query, int32_t k,
+                       float* distances_sq, int32_t* indices, size_t* n_neighbors, uint64_t* total );
+
 /* ---- point-to-plane ICP ------------------------------------------------------------- */
 
 /* icp_align (lib/rs/icp.h:416-500): aligns T1*source to T2*target; *T1 is updated in place,

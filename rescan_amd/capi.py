@@ -37,6 +37,12 @@ SIGNATURES = {
     "rs_hip_cloud_build_seconds": (C.c_int64, [C.POINTER(C.c_double), C.c_int32]),
     "rs_hip_radius_search": (C.c_int, [C.c_void_p, f32p, C.c_int64, C.c_float, C.c_int32, f32p, i32p, u64p,
                                        C.POINTER(C.c_uint64)]),
+    "rs_hip_knn_grid_create": (C.c_void_p, [C.c_void_p, C.c_float, C.c_int32]),
+    "rs_hip_knn_grid_destroy": (None, [C.c_void_p]),
+    "rs_hip_knn_grid_geometry": (C.c_int, [C.c_void_p, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"), C.POINTER(C.c_double), f32p]),
+    "rs_hip_knn_geometry": (C.c_int, [f32p, C.c_int64, C.c_float, C.c_int32, np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS"),
+                                      C.POINTER(C.c_double), f32p]),
+    "rs_hip_knn_search": (C.c_int, [C.c_void_p, f32p, C.c_int64, C.c_int32, f32p, i32p, u64p, C.POINTER(C.c_uint64)]),
     "rs_hip_icp_align": (C.c_int, [C.c_void_p, C.c_void_p, f32p, f32p, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                    C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "rs_hip_icp_align_traced": (C.c_int, [C.c_void_p, C.c_void_p, f32p, f32p, C.c_float, C.c_float, C.c_int32, C.c_int32,
@@ -239,6 +245,57 @@ def radius_search(target, query, radius, k):
     d = np.zeros((nq, k), np.float32); i = np.zeros((nq, k), np.int32); nn = np.zeros(nq, np.uint64)
     tot = C.c_uint64()
     _check(load().rs_hip_radius_search(target.handle, query, nq, float(radius), int(k), d, i, nn, C.byref(tot)))
+    return d, i, nn.astype(np.int64), tot.value
+
+
+KNN_MAX_K = 64          # RS_HIP_KNN_MAX_K
+
+
+class KnnGrid:
+    """msh_hash_grid_knn_search's own grid (geometry from the init radius) over a device cloud's points (rs_hip_knn_grid_t).
+    dim = 2: a cloud of (x, y, 0) points, as msh_hash_grid_init_2d keeps them."""
+
+    def __init__(self, cloud, radius, dim=3):
+        lib = load()
+        self.dim = int(dim)
+        self.handle = lib.rs_hip_knn_grid_create(cloud.handle, float(radius), self.dim)
+        if not self.handle:
+            raise RescanHipError("rs_hip_knn_grid_create failed: " + lib.rs_hip_last_error().decode())
+
+    def geometry(self):
+        """((w, h, d), cell, min_pt) of the grid."""
+        dims = np.zeros(3, np.int64); cell = C.c_double(); mn = np.zeros(3, np.float32)
+        _check(load().rs_hip_knn_grid_geometry(self.handle, dims, C.byref(cell), mn))
+        return tuple(int(x) for x in dims), cell.value, mn
+
+    def close(self):
+        if getattr(self, "handle", None):
+            load().rs_hip_knn_grid_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def knn_geometry(points, radius, dim=3):
+    """The k-NN grid's ((w, h, d), cell, min_pt) for these points, computed on the host (no device needed)."""
+    pts = _f32(points).reshape(-1, 3)
+    dims = np.zeros(3, np.int64); cell = C.c_double(); mn = np.zeros(3, np.float32)
+    _check(load().rs_hip_knn_geometry(pts, len(pts), float(radius), int(dim), dims, C.byref(cell), mn))
+    return tuple(int(x) for x in dims), cell.value, mn
+
+
+def knn_search(grid, query, k):
+    """msh_hash_grid_knn_search: the reference's k-NN rows (k <= KNN_MAX_K), ascending; entries past a row's count are 0.
+    Returns (d², idx, n_neighbors, total) like radius_search."""
+    query = _f32(query).reshape(-1, 3)
+    nq = len(query)
+    d = np.zeros((nq, k), np.float32); i = np.zeros((nq, k), np.int32); nn = np.zeros(nq, np.uint64)
+    tot = C.c_uint64()
+    _check(load().rs_hip_knn_search(grid.handle, query, nq, int(k), d, i, nn, C.byref(tot)))
     return d, i, nn.astype(np.int64), tot.value
 
 

@@ -2670,3 +2670,13 @@ extern "C" int rs_hip_coverage_scores( rs_hip_coverage_t* c, const rs_hip_cloud_
   }
   return RS_HIP_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// what the translation units with entry points of their own (rs_knn.hip) need from this one
+// ------------------------------------------------------------------------------------------
+
+namespace rs {
+int api_ready( hipStream_t* st ) { const int rc = ensure_ready(); if( rc == RS_HIP_OK ) *st = g_stream; return rc; }
+void api_set_err( const char* what ) { set_err( "%s", what ); }
+const GridView* api_cloud_view( const rs_hip_cloud* c ) { return c ? &c->view : nullptr; }
+} // namespace rs

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+struct rs_hip_cloud;
+
 namespace rs {
 
 // Device view of a cloud: 16-byte records sorted by grid cell, cell offset table.
@@ -365,5 +367,10 @@ struct EdgeLaunch
 void launch_edge_count( const EdgeLaunch& L, hipStream_t st );   // fills count
 void launch_edge_scan( const EdgeLaunch& L, hipStream_t st );    // count -> offset (single workgroup, fixed order)
 void launch_edge_write( const EdgeLaunch& L, hipStream_t st );   // fills e1/e2/ew
+
+// rs_api.hip's runtime state for entry points defined in other translation units (rs_knn.hip)
+int             api_ready( hipStream_t* st );              // ensure_ready(); *st = the calling thread's stream
+void            api_set_err( const char* what );           // rs_hip_last_error()'s text
+const GridView* api_cloud_view( const struct ::rs_hip_cloud* c );
 
 } // namespace rs

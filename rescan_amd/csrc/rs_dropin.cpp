@@ -49,8 +49,9 @@ struct Stats
 {
   bool on = getenv( "RS_DROPIN_STATS" ) != nullptr;
   struct Row { const char* name; unsigned long long calls = 0, items = 0; double seconds = 0.0; };
-  Row rows[8] = { { "grid init (host index)" }, { "grid device index (lazy)" }, { "radius_search, host path" }, { "radius_search, device path" },
-                  { "icp_align" }, { "scores (flat entry)" }, { "labels (flat entry)" }, { "other" } };
+  Row rows[10] = { { "grid init (host index)" }, { "grid device index (lazy)" }, { "radius_search, host path" }, { "radius_search, device path" },
+                   { "icp_align" }, { "scores (flat entry)" }, { "labels (flat entry)" }, { "other" },
+                   { "knn grid, device (lazy)" }, { "knn_search, device path" } };
   ~Stats()
   {
     if( !on ) return;
@@ -438,7 +439,9 @@ struct GridHandle
   bool dev_failed = false;
   int dim = 3;                        // 2: msh_hash_grid_init_2d — points and queries are (x, y), kept as (x, y, 0)
   float radius = 0.0f;                // as given to init (the k-NN grid's geometry)
-  std::unique_ptr<KnnGrid> knn;       // built at the first msh_hash_grid_knn_search
+  std::unique_ptr<KnnGrid> knn;       // built at the first msh_hash_grid_knn_search served on the host
+  rs_hip_knn_grid_t* knn_dev = nullptr;   // built at the first msh_hash_grid_knn_search served on the device
+  bool knn_dev_failed = false;
   std::mutex mutex;
 };
 
@@ -456,6 +459,17 @@ rs_hip_cloud_t* device_cloud_of( GridHandle* h )
   h->dev = rs_hip_cloud_create( pts.data(), nullptr, h->host.n, h->host.cell );
   if( !h->dev ) { h->dev_failed = true; complain( "msh_hash_grid: device index" ); }
   return h->dev;
+}
+
+rs_hip_knn_grid_t* device_knn_of( GridHandle* h )
+{
+  rs_hip_cloud_t* c = device_cloud_of( h );
+  std::lock_guard<std::mutex> lock( h->mutex );
+  if( h->knn_dev || h->knn_dev_failed || !c ) return h->knn_dev;
+  Timed t( 8, (unsigned long long)h->host.n );
+  h->knn_dev = rs_hip_knn_grid_create( c, h->radius, h->dim );
+  if( !h->knn_dev ) { h->knn_dev_failed = true; complain( "msh_hash_grid_knn_search: device grid (the host path serves this grid)" ); }
+  return h->knn_dev;
 }
 
 } // namespace
@@ -512,6 +526,7 @@ void msh_hash_grid_term( rsd_hash_grid_t* hg )
   {
     GridHandle* h = (GridHandle*)hg->data_buffer;
     invalidate_pointer( h->src );                        // whatever else was built from that array goes with its grid
+    if( h->knn_dev ) rs_hip_knn_grid_destroy( h->knn_dev );
     if( h->dev ) rs_hip_cloud_destroy( h->dev );
     delete h;
   }
@@ -586,7 +601,9 @@ static size_t radius_search_3d( GridHandle* h, rsd_search_desc_t* d )
   return host_search_all( h, d );
 }
 
-// msh_hash_grid.h:1294-1447 — see KnnGrid.  Host code: no caller of the hot path uses it; rows ascending in (dist², index).
+// msh_hash_grid.h:1294-1447 — see KnnGrid; rows ascending in (dist², index).  Calls of more than RS_DROPIN_HOST_QUERIES queries
+// with k <= RS_HIP_KNN_MAX_K go to the device (rs_hip_knn_search, the same rows: tests/test_gpu_knn.py), on a k-NN grid built at the
+// first such call and kept with the handle; the rest — and a call whose device grid or search failed — are served by KnnGrid here.
 size_t msh_hash_grid_knn_search( const rsd_hash_grid_t* hg, rsd_search_desc_t* d )
 {
   if( !hg || !d || !d->query_pts || !d->distances_sq || !d->indices || d->k == 0 ) return 0;
@@ -596,6 +613,30 @@ size_t msh_hash_grid_knn_search( const rsd_hash_grid_t* hg, rsd_search_desc_t* d
     return 0;
   }
   GridHandle* h = (GridHandle*)hg->data_buffer;
+  const size_t host_queries = getenv( "RS_DROPIN_HOST_QUERIES" ) ? (size_t)atoll( getenv( "RS_DROPIN_HOST_QUERIES" ) ) : 4;      // (as for radius search)
+  if( d->n_query_pts > host_queries && d->k <= RS_HIP_KNN_MAX_K )
+  {
+    rs_hip_knn_grid_t* kg = device_knn_of( h );
+    if( kg )
+    {
+      std::vector<float> q3;
+      const float* q = d->query_pts;
+      if( h->dim == 2 )
+      {
+        q3.resize( d->n_query_pts * 3 );
+        for( size_t i = 0; i < d->n_query_pts; ++i ) { q3[3 * i] = d->query_pts[2 * i]; q3[3 * i + 1] = d->query_pts[2 * i + 1]; q3[3 * i + 2] = 0.0f; }
+        q = q3.data();
+      }
+      uint64_t total = 0;
+      Timed t( 9, d->n_query_pts );
+      const int rc = rs_hip_knn_search( kg, q, (int64_t)d->n_query_pts, (int32_t)d->k, d->distances_sq, d->indices, d->n_neighbors, &total );
+      if( rc == RS_HIP_OK ) return (size_t)total;
+      complain( "msh_hash_grid_knn_search" );
+      if( g_device_failures.fetch_add( 1 ) == 0 )
+        fprintf( stderr, "[rescan_hip] msh_hash_grid_knn_search: the device path failed; this call and any later failing one are answered "
+                         "on the host (slow).  rsd_device_failures() counts them.\n" );
+    }
+  }
   {
     std::lock_guard<std::mutex> lock( h->mutex );
     if( !h->knn ) { h->knn.reset( new KnnGrid() ); h->knn->build( h->host, h->radius ); }
