@@ -144,6 +144,23 @@ int rs_hip_icp_align_traced( const rs_hip_cloud_t* source, const rs_hip_cloud_t*
                              float* T1, const float* T2, float max_dist, float max_angle,
                              int32_t max_iter, int32_t fixed_iters, float* err, int32_t* n_iters, float* errs_per_iter );
 
+/* Per-iteration trace of the calling thread's ICP calls (rs_hip_icp_align, _batch — slices included — and _multi) from
+ * rs_hip_icp_trace_begin to rs_hip_icp_trace_end.  For problem p (its index in the call) and iteration i < max_iter, row
+ * r = p * max_iter + i receives the pose after the iteration (poses[16 r ..]), its error (errs[r]) and the estimator step that
+ * ran (kinds[r], RS_HIP_ICP_STEP_*); rows of iterations that did not run keep kind RS_HIP_ICP_STEP_NONE and NaN.  A problem run
+ * again in the reference's order by the stop test's guard has the rows of the run whose result is returned and redone[p] = 1.
+ * Same results as untraced; the loop state is read after every iteration.  Begin fills every row and redone[] afresh. */
+#define RS_HIP_ICP_STEP_NONE        -1
+#define RS_HIP_ICP_STEP_REF_ORDER    0   /* the reference's own accumulation order (k_icp_faithful): its bits */
+#define RS_HIP_ICP_STEP_REPLAY       1   /* the same bits in parallel (rs_hip_icp_replay_below) */
+#define RS_HIP_ICP_STEP_LANE_CHAINS  2   /* the reference's fp32 centroid chains by one wave per chain + fp64 moments */
+#define RS_HIP_ICP_STEP_GRID_CHAINS  3   /* the same chains spread over the chip + fp64 moments */
+#define RS_HIP_ICP_STEP_PLAIN        4   /* early plain step: fp64 moments centred on their own fp64 centroids (rs_hip_icp_early_plain) */
+#define RS_HIP_ICP_STEP_RECORDS      5   /* the chains' sums by pass 2 of the replay from the searches' records (after the chains gave up) */
+#define RS_HIP_ICP_STEP_MOMENTS      6   /* plain k_icp_moments (rs_hip_icp_exact_centroids( 0 )) */
+int rs_hip_icp_trace_begin( float* poses, float* errs, int32_t* kinds, int32_t* redone, int32_t max_iter, int32_t n_problems );
+int rs_hip_icp_trace_end( void );
+
 /* The estimator step (icp.h:136-148,210-298,393-402), by source size (round 6; priced against the bar on every reference fixture:
  * profiles/r06/estimator_policy.txt).  Sources of at most `n_points` points use the reference's own accumulation order and
  * precisions (one sequential fp32 chain per accumulator): poses, errors and iteration counts are bit-identical to the

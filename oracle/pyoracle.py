@@ -62,6 +62,7 @@ class _Base:
                                        [C.c_void_p, f32p, C.c_int64, C.c_float, C.c_int64, C.c_int,
                                         f32p, i32p, i64p])
         self._icp_estimate = self._fn("icp_estimate_pt2pl", C.c_float, [f32p, f32p, f32p, f32p, C.c_int32, f32p])
+        self._weighted_centroid = self._fn("weighted_centroid", None, [f32p, f32p, C.c_int32, f32p])
 
     # -- helpers ---------------------------------------------------------------------
     def mat4_inverse(self, m):
@@ -108,6 +109,10 @@ class _Base:
         total = self._radius_search(g, query, nq, float(radius), int(k), int(sort), d, i, nn)
         return d, i, nn, total
 
+    def weighted_centroid(self, pts, w):
+        """icp__compute_weighted_centroid (icp.h:136-148): float32[3]."""
+        o = np.zeros(3, np.float32); w = _f32(w); self._weighted_centroid(_f32(pts), w, len(w), o); return o
+
     def icp_estimate_pt2pl(self, p1, p2, n2, w, T1):
         T = _f32(T1).ravel().copy()
         err = self._icp_estimate(_f32(p1), _f32(p2), _f32(n2), _f32(w), len(w), T)
@@ -126,6 +131,9 @@ class Oracle(_Base):
         self._find_corrs = self._fn("icp_find_corrs", C.c_int32,
                                     [f32p, f32p, C.c_int32, f32p, f32p, C.c_int32, C.c_void_p, f32p, f32p,
                                      C.c_float, C.c_float, f32p, f32p, f32p, f32p, f32p])
+        self._find_corrs_uncut = self._fn("icp_find_corrs_uncut", C.c_int32,
+                                          [f32p, f32p, C.c_int32, f32p, f32p, C.c_int32, C.c_void_p, f32p, f32p,
+                                           C.c_float, C.c_float, f32p, f32p, f32p, f32p, f32p, f32p, f32p])
         self._icp_align = self._fn("icp_align", C.c_float,
                                    [f32p, f32p, C.c_int32, f32p, f32p, C.c_int32, f32p, f32p, C.c_float, C.c_float,
                                     C.POINTER(C.c_int32)])
@@ -147,6 +155,17 @@ class Oracle(_Base):
                               float(max_dist), float(max_angle), *out, w)
         self.grid_destroy(g)
         return [o[:nc] for o in out] + [w[:nc]]
+
+    def icp_find_corrs_uncut(self, grid2, pts1, nor1, pts2, nor2, T1, T2, max_dist, max_angle):
+        """icp_find_corrs against a grid of pts2 made by grid_create (icp_align builds it once, with the first max_dist):
+        (c_pts1, c_nor1, c_pts2, c_nor2, w, d2, w_uncut) — w with the reference's 2.5 sigma cut, w_uncut before it."""
+        pts1, nor1, pts2, nor2 = map(_f32, (pts1, nor1, pts2, nor2))
+        n1 = len(pts1)
+        out = [np.zeros((max(n1, 1), 3), np.float32) for _ in range(4)]
+        w, d2, wu = (np.zeros(max(n1, 1), np.float32) for _ in range(3))
+        nc = self._find_corrs_uncut(pts1, nor1, n1, pts2, nor2, len(pts2), grid2, _f32(T1).ravel(), _f32(T2).ravel(),
+                                    float(max_dist), float(max_angle), *out, w, d2, wu)
+        return [o[:nc] for o in out] + [w[:nc], d2[:nc], wu[:nc]]
 
     def icp_align(self, pts1, nor1, pts2, nor2, T1, T2, max_dist, max_angle):
         pts1, nor1, pts2, nor2 = map(_f32, (pts1, nor1, pts2, nor2))

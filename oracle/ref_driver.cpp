@@ -224,6 +224,12 @@ int32_t ref_icp_iterate( float* pts1, float* nor1, int32_t n1, float* pts2, floa
   return done;
 }
 
+void ref_weighted_centroid( float* pts, float* w, int32_t n, float* out )
+{
+  msh_vec3_t c = icp__compute_weighted_centroid( (msh_vec3_t*)pts, w, n );
+  out[0] = c.x; out[1] = c.y; out[2] = c.z;
+}
+
 float ref_icp_estimate_pt2pl( float* p1, float* p2, float* n2, float* w, int32_t n, float* T1 )
 {
   msh_mat4_t t1; memcpy( t1.data, T1, 64 );

@@ -604,11 +604,12 @@ int orc_label_gate( float dot )
  * Point-to-plane ICP  (lib/rs/icp.h)
  * ---------------------------------------------------------------------------------------- */
 
-/* :306-412 with caller-provided output arrays */
-int32_t orc_icp_find_corrs( const float* pts1, const float* nor1, int32_t n1,
-                            const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
-                            const float* T1, const float* T2, float max_dist, float max_angle,
-                            float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w )
+/* :306-412 with caller-provided output arrays; d2_out / w_uncut (may be NULL): every correspondence's dist² and its weight before
+   the 2.5 sigma cut */
+static int32_t find_corrs_impl( const float* pts1, const float* nor1, int32_t n1,
+                                const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
+                                const float* T1, const float* T2, float max_dist, float max_angle,
+                                float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w, float* d2_out, float* w_uncut )
 {
   (void)n2;
   enum { MAX_NN = 16 };
@@ -655,6 +656,8 @@ int32_t orc_icp_find_corrs( const float* pts1, const float* nor1, int32_t n1,
       v3_store( c_nor2, ic, v3_load( nor2, best ) );
       w[ic] = ( 1.0f - dist / max_dist ) * dot;          /* :387 dist² over un-squared radius */
       dists[ic] = dist;                                   /* :388 compaction in place */
+      if( d2_out ) { d2_out[ic] = dist; }
+      if( w_uncut ) { w_uncut[ic] = w[ic]; }
       ic++;
     }
   }
@@ -671,6 +674,23 @@ int32_t orc_icp_find_corrs( const float* pts1, const float* nor1, int32_t n1,
   return ic;
 }
 
+int32_t orc_icp_find_corrs( const float* pts1, const float* nor1, int32_t n1,
+                            const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
+                            const float* T1, const float* T2, float max_dist, float max_angle,
+                            float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w )
+{
+  return find_corrs_impl( pts1, nor1, n1, pts2, nor2, n2, index2, T1, T2, max_dist, max_angle, c_pts1, c_nor1, c_pts2, c_nor2, w, NULL, NULL );
+}
+
+/* the same search, also returning every correspondence's dist² and uncut weight (tests/icp_restate.py models cuts of its own) */
+int32_t orc_icp_find_corrs_uncut( const float* pts1, const float* nor1, int32_t n1,
+                                  const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
+                                  const float* T1, const float* T2, float max_dist, float max_angle,
+                                  float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w, float* d2, float* w_uncut )
+{
+  return find_corrs_impl( pts1, nor1, n1, pts2, nor2, n2, index2, T1, T2, max_dist, max_angle, c_pts1, c_nor1, c_pts2, c_nor2, w, d2, w_uncut );
+}
+
 /* :136-148 */
 static v3 weighted_centroid( const float* pts, const float* w, int32_t n )
 {
@@ -683,6 +703,12 @@ static v3 weighted_centroid( const float* pts, const float* w, int32_t n )
   }
   float inv = 1.0f / total;                     /* msh_vec3_scalar_div, msh_vec_math.h:754-758 */
   return v3_scale( c, inv );
+}
+
+void orc_weighted_centroid( const float* pts, const float* w, int32_t n, float* out )
+{
+  v3 c = weighted_centroid( pts, w, n );
+  out[0] = c.x; out[1] = c.y; out[2] = c.z;
 }
 
 /* lib/rs/lineqn.h:153-196 (N = 6 takes the general branch) */

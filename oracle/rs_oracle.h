@@ -68,6 +68,13 @@ int32_t orc_icp_find_corrs( const float* pts1, const float* nor1, int32_t n1,
                             const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
                             const float* T1, const float* T2, float max_dist, float max_angle,
                             float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w );
+/* the same, also every correspondence's dist² (d2) and its weight before the 2.5 sigma cut (w_uncut), capacity n1 each */
+int32_t orc_icp_find_corrs_uncut( const float* pts1, const float* nor1, int32_t n1,
+                                  const float* pts2, const float* nor2, int32_t n2, const orc_grid_t* index2,
+                                  const float* T1, const float* T2, float max_dist, float max_angle,
+                                  float* c_pts1, float* c_nor1, float* c_pts2, float* c_nor2, float* w, float* d2, float* w_uncut );
+/* icp__compute_weighted_centroid (lib/rs/icp.h:136-148): the sequential fp32 chains, out = 3 floats */
+void orc_weighted_centroid( const float* pts, const float* w, int32_t n, float* out );
 /* lib/rs/icp.h:210-298 */
 float orc_icp_estimate_pt2pl( const float* p1, const float* p2, const float* n2, const float* w,
                               int32_t n, float* T1 );

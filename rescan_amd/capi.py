@@ -47,6 +47,8 @@ SIGNATURES = {
                                    C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
     "rs_hip_icp_align_traced": (C.c_int, [C.c_void_p, C.c_void_p, f32p, f32p, C.c_float, C.c_float, C.c_int32, C.c_int32,
                                           C.POINTER(C.c_float), C.POINTER(C.c_int32), f32p]),
+    "rs_hip_icp_trace_begin": (C.c_int, [f32p, f32p, i32p, i32p, C.c_int32, C.c_int32]),
+    "rs_hip_icp_trace_end": (C.c_int, []),
     "rs_hip_icp_reference_order_below": (C.c_int32, [C.c_int32]),
     "rs_hip_icp_replay_below": (C.c_int32, [C.c_int32]),
     "rs_hip_icp_lane_chains_below": (C.c_int32, [C.c_int32]),
@@ -407,6 +409,35 @@ def icp_align_traced(source, target, T1, T2=IDENTITY, max_dist=0.1, max_angle=np
                                           float(np.float32(max_angle)), int(max_iter), int(bool(fixed_iters)),
                                           C.byref(err), C.byref(it), errs))
     return err.value, T, it.value, errs[: it.value].copy()
+
+
+# rs_hip_icp_trace_begin's estimator codes (include/rescan_hip.h: RS_HIP_ICP_STEP_*)
+ICP_STEP_NONE, ICP_STEP_REF_ORDER, ICP_STEP_REPLAY, ICP_STEP_LANE_CHAINS, ICP_STEP_GRID_CHAINS, ICP_STEP_PLAIN, \
+    ICP_STEP_RECORDS, ICP_STEP_MOMENTS = -1, 0, 1, 2, 3, 4, 5, 6
+ICP_STEP_NAMES = {-1: "none", 0: "ref_order", 1: "replay", 2: "lane_chains", 3: "grid_chains", 4: "plain", 5: "records",
+                  6: "moments"}
+
+
+class IcpTrace:
+    """The calling thread's ICP calls inside ``with IcpTrace(max_iter, n_problems) as tr:`` leave, per problem p and
+    iteration i, the pose after the iteration (tr.poses[p, i], 16 floats), its error (tr.errs[p, i]) and the estimator step
+    that ran (tr.kinds[p, i], ICP_STEP_*; ICP_STEP_NONE where no iteration ran); tr.redone[p] = 1 where the stop test's
+    guard ran the problem again in the reference's order (rs_hip_icp_trace_begin)."""
+
+    def __init__(self, max_iter, n_problems):
+        self.poses = np.zeros((int(n_problems), int(max_iter), 16), np.float32)
+        self.errs = np.zeros((int(n_problems), int(max_iter)), np.float32)
+        self.kinds = np.zeros((int(n_problems), int(max_iter)), np.int32)
+        self.redone = np.zeros(int(n_problems), np.int32)
+
+    def __enter__(self):
+        _check(load().rs_hip_icp_trace_begin(self.poses.reshape(-1), self.errs.reshape(-1), self.kinds.reshape(-1),
+                                              self.redone, self.poses.shape[1], self.poses.shape[0]))
+        return self
+
+    def __exit__(self, *exc):
+        _check(load().rs_hip_icp_trace_end())
+        return False
 
 
 def icp_align_batch(source, target, T1s, T2=IDENTITY, max_dist=0.1, max_angle=np.deg2rad(60.0), max_iter=100,

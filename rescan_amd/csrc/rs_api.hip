@@ -119,6 +119,55 @@ thread_local Workspace g_ws;
 // reads its state after every iteration instead of every few)
 thread_local float* g_icp_trace = nullptr;
 thread_local int g_icp_trace_cap = 0;
+// rs_hip_icp_trace_begin: the calling thread's ICP calls leave, per problem and iteration, the pose after it, its error and the
+// estimator that ran (RS_HIP_ICP_STEP_*), until rs_hip_icp_trace_end.  A call's problem index reaches the trace's through
+// g_tr_map / g_tr_off (slices, groups of a multi-source batch, problems run again): global = map ? map[off + p] : off + p.
+struct IcpStepTrace { float* poses = nullptr; float* errs = nullptr; int32_t* kinds = nullptr; int32_t* redone = nullptr; int max_iter = 0, n_prob = 0; };
+thread_local IcpStepTrace g_tr;
+thread_local const int* g_tr_map = nullptr;
+thread_local int g_tr_off = 0;
+struct TrShift      // problem p of the calls below is problem d + p of the caller
+{
+  int saved; TrShift( int d ) : saved( g_tr_off ) { g_tr_off += d; } ~TrShift() { g_tr_off = saved; }
+};
+struct TrMap        // problem p of the calls below is the caller's problem map[p]
+{
+  const int* saved_map; int saved_off;
+  TrMap( const int* map ) : saved_map( g_tr_map ), saved_off( g_tr_off ) { g_tr_map = map; g_tr_off = 0; }
+  ~TrMap() { g_tr_map = saved_map; g_tr_off = saved_off; }
+};
+inline int tr_global( int p )
+{
+  const int g = g_tr_map ? g_tr_map[g_tr_off + p] : g_tr_off + p;
+  return ( g >= 0 && g < g_tr.n_prob ) ? g : -1;
+}
+void tr_clear_row( int g )
+{
+  for( int i = 0; i < g_tr.max_iter; ++i )
+  {
+    const size_t r = (size_t)g * g_tr.max_iter + i;
+    for( int k = 0; k < 16; ++k ) g_tr.poses[r * 16 + k] = NAN;
+    g_tr.errs[r] = NAN; g_tr.kinds[r] = RS_HIP_ICP_STEP_NONE;
+  }
+}
+// a call starts over for its problems 0 .. n-1: whatever an earlier attempt left in their rows goes
+void tr_clear( int n ) { if( g_tr.kinds ) for( int p = 0; p < n; ++p ) { const int g = tr_global( p ); if( g >= 0 ) tr_clear_row( g ); } }
+// iteration i has just run for every problem with was_active[p]: its pose and error as the state holds them now (hS: the n-problem state)
+void tr_record( int n, int i, int kind, const float* hS, std::vector<char>& was_active )
+{
+  const size_t np = (size_t)n;
+  const int* hActive = (const int*)( hS + np * 16 );
+  for( int p = 0; p < n; ++p )
+  {
+    if( !was_active[p] ) continue;
+    was_active[p] = hActive[p] ? 1 : 0;
+    const int g = tr_global( p );
+    if( g < 0 || i >= g_tr.max_iter ) continue;
+    const size_t r = (size_t)g * g_tr.max_iter + i;
+    std::memcpy( g_tr.poses + r * 16, hS + 16 * p, 64 ); g_tr.errs[r] = hS[np * 34 + p]; g_tr.kinds[r] = kind;
+  }
+}
+void tr_mark_redone( int p ) { if( g_tr.redone ) { const int g = tr_global( p ); if( g >= 0 ) g_tr.redone[g] = 1; } }
 DevBuf g_faith_redone;            // (a process-wide counter: rs_hip_icp_faith_redone)
 std::mutex g_faith_redone_mu;
 
@@ -1086,6 +1135,7 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
   if( !T1s || !T2 || !errs ) { set_err( "icp_align: null argument" ); return RS_HIP_E_ARG; }
   IcpCtx cx;
   if( ( rc = icp_prepare( cx, source, target, n, T2 ) ) ) return rc;
+  tr_clear( n );
   const float tmin = icp_gate_threshold( max_angle );
   if( source->n == 0 ) { for( int p = 0; p < n; ++p ) { errs[p] = 1e6f; if( iters ) iters[p] = 1; } return RS_HIP_OK; }   // n_corrs == 0 on the first search
   if( ( rc = icp_enable_certificates( cx ) ) ) return rc;
@@ -1199,11 +1249,13 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
   const int n_plain = ( chains || from_records ) ? icp_plain_iterations( source->n, max_iter, fixed_iters != 0 ) : 0;
   if( ( rc = icp_fills_flush() ) ) return rc;      // everything the call's first kernels expect zeroed, in one launch
   ProfChain prof;
+  int kind = RS_HIP_ICP_STEP_NONE;                  // (rs_hip_icp_trace_begin: the estimator of the iteration just enqueued)
+  std::vector<char> was_active( g_tr.kinds ? np : 0, 1 );
   for( int i = 0; i < max_iter; )                                       // icp.h:444
   {
     // (the stop test looks at i > 5, icp.h:489: the first seven iterations go out in one piece, then chunk_env at a time — an iteration enqueued
     //  behind the one that stopped is six empty launches, a look at the state a copy and a synchronisation)
-    const int chunk = ( debug || g_icp_trace ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
+    const int chunk = ( debug || g_icp_trace || g_tr.kinds ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
     for( int c = 0; c < chunk; ++c, ++i )
     {
       icp_set_radius( cx, max_dist, tmin );
@@ -1225,7 +1277,7 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
       prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
       if( debug ) icp_debug_after( cx, source->n, n, i, max_dist );
       prof.mark( "icp_moments" );
-      if( replay ) launch_icp_replay( cx.L, RB, g_stream );
+      if( replay ) { launch_icp_replay( cx.L, RB, g_stream ); kind = RS_HIP_ICP_STEP_REPLAY; }
       else if( chains )
       {
         // the binade guesses of the chains' records: made from the sums of the iteration before (k_chain_walk_and_moments) — in the first
@@ -1233,19 +1285,20 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
         if( i < n_plain )
         {
           IcpLaunch Lp = cx.L; Lp.exact_centroids = 0;
-          launch_icp_plain_from_records( Lp, CB, g_stream );
+          launch_icp_plain_from_records( Lp, CB, g_stream ); kind = RS_HIP_ICP_STEP_PLAIN;
         }
         else
         {
           CB.refresh = ( i == n_plain || ( chain_refresh > 0 && ( i % chain_refresh ) == 0 ) ) ? 1 : 0;
-          launch_icp_chain_centroids( cx.L, CB, g_stream );
+          launch_icp_chain_centroids( cx.L, CB, g_stream ); kind = RS_HIP_ICP_STEP_GRID_CHAINS;
         }
       }
-      else if( lane ) launch_icp_lane_chains( cx.L, CB, g_stream );
-      else if( from_records && i < n_plain ) { IcpLaunch Lp = cx.L; Lp.exact_centroids = 0; launch_icp_plain_from_records( Lp, CB, g_stream ); }
-      else if( from_records ) launch_icp_exact_centroids_from_records( cx.L, RB, CB, g_stream );
-      else if( exact_centroids ) launch_icp_exact_centroids( cx.L, RB, g_stream );
-      else if( cx.L.faith ) launch_icp_faithful( cx.L, g_stream ); else launch_icp_moments( cx.L, g_stream );
+      else if( lane ) { launch_icp_lane_chains( cx.L, CB, g_stream ); kind = RS_HIP_ICP_STEP_LANE_CHAINS; }
+      else if( from_records && i < n_plain ) { IcpLaunch Lp = cx.L; Lp.exact_centroids = 0; launch_icp_plain_from_records( Lp, CB, g_stream ); kind = RS_HIP_ICP_STEP_PLAIN; }
+      else if( from_records ) { launch_icp_exact_centroids_from_records( cx.L, RB, CB, g_stream ); kind = RS_HIP_ICP_STEP_RECORDS; }
+      else if( exact_centroids ) { launch_icp_exact_centroids( cx.L, RB, g_stream ); kind = RS_HIP_ICP_STEP_RECORDS; }
+      else if( cx.L.faith ) { launch_icp_faithful( cx.L, g_stream ); kind = RS_HIP_ICP_STEP_REF_ORDER; }
+      else { launch_icp_moments( cx.L, g_stream ); kind = RS_HIP_ICP_STEP_MOMENTS; }
       double nd = max_dist * 0.95;                                      // icp.h:493
       max_dist = (float)( nd > 0.05 ? nd : 0.05 );
     }
@@ -1253,6 +1306,7 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
     HIP_TRY( hipMemcpyAsync( hS, g_ws.state.p, state_bytes, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
     HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
     if( g_icp_trace && n == 1 && i >= 1 && i - 1 < g_icp_trace_cap ) g_icp_trace[i - 1] = hS[np * 34];      // the error after iteration i - 1
+    if( g_tr.kinds ) tr_record( n, i - 1, kind, hS, was_active );
     int n_active = 0;
     for( int p = 0; p < n; ++p ) n_active += hActive[p] ? 1 : 0;
     if( n_active == 0 ) break;
@@ -1337,6 +1391,8 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
   // The estimators of large sources keep per-point records per problem (48 B with the chains, 44 B + the replay's rows when they
   // give up): many start poses of a whole scan are run in slices of problems whose records stay below RS_HIP_ICP_BATCH_BYTES
   // (default 4 GB) — the problems are independent, so the results are those of the one batch.
+  // (the arguments first: nothing below may read through them before they are known to be there)
+  if( !source || !target || !T1s || !T2 || !errs || n < 0 ) { set_err( "icp_align_batch: bad arguments" ); return RS_HIP_E_ARG; }
   static const double cap = getenv( "RS_HIP_ICP_BATCH_BYTES" ) ? atof( getenv( "RS_HIP_ICP_BATCH_BYTES" ) ) : 4e9;
   const bool per_point_records = source && source->n > g_ref_order_below.load();
   // (96 B per point: the 48-byte records + what a slice that falls back to the replay adds — its segment rows, ~35 / 128 x ( 8 + 24 + sizeof( ReplaySeg ) ) ≈ 48 B per point)
@@ -1352,6 +1408,7 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
     // (the start poses are kept: a problem whose stop test falls inside the guard is run again from its own)
     std::vector<float> T_in( T, T + 16 * (size_t)np );
     std::vector<int> edge;
+    TrShift ts( p0 );
     int rc = icp_align_batch_impl( source, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode, false, &edge );
     // (a problem of the slice whose chains gave up: that slice again, its seven sums by pass 2 of the replay — nothing of it was written yet)
     if( rc == ICP_CHAINS_GAVE_UP )
@@ -1366,8 +1423,10 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
       for( int q : edge )
       {
         std::memcpy( T + 16 * (size_t)q, T_in.data() + 16 * (size_t)q, 64 );
-        int rc2 = icp_align_batch_impl( source, target, T + 16 * (size_t)q, 1, T2, max_dist, max_angle, max_iter, fixed_iters, e + q, it ? it + q : nullptr, mode, true );
+        int rc2;
+        { TrShift tq( q ); rc2 = icp_align_batch_impl( source, target, T + 16 * (size_t)q, 1, T2, max_dist, max_angle, max_iter, fixed_iters, e + q, it ? it + q : nullptr, mode, true ); }
         if( rc2 ) return rc2;
+        tr_mark_redone( q );
         g_stop_guard_redone.fetch_add( 1 );
       }
       rc = RS_HIP_OK;
@@ -1399,8 +1458,8 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
                             float* T1s, int32_t n, const float* T2, float max_dist, float max_angle,
                             int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters )
 {
+  if( !sources || !target || !T1s || !T2 || !errs || n < 0 ) { set_err( "icp_align_multi: bad arguments" ); return RS_HIP_E_ARG; }
   int rc = ensure_ready(); if( rc ) return rc;
-  if( !sources || !T1s || !T2 || !errs || n < 0 ) { set_err( "icp_align_multi: bad arguments" ); return RS_HIP_E_ARG; }
   if( n == 0 ) return RS_HIP_OK;
   // Every problem gets the estimator its own rs_hip_icp_align would (icp_estimator_class), so that its result is that call's bit for
   // bit: the problems within the reference-order range run as one batch (k_icp_faithful), those within the lane chains' range as
@@ -1412,7 +1471,10 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
     group[sources[p]->n > 0 ? icp_estimator_class( sources[p]->n ) : 2].push_back( p );
   }
   for( int p : group[2] )
+  {
+    TrShift ts( p );
     if( ( rc = rs_hip_icp_align_batch( sources[p], target, T1s + 16 * p, 1, T2, max_dist, max_angle, max_iter, fixed_iters, errs + p, iters ? iters + p : nullptr ) ) ) return rc;
+  }
   for( int cls = 0; cls < 2; ++cls )
   {
     const std::vector<int>& g = group[cls];
@@ -1420,6 +1482,7 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
     if( g.size() == 1 )
     {
       const int p = g[0];
+      TrShift ts( p );
       if( ( rc = rs_hip_icp_align_batch( sources[p], target, T1s + 16 * p, 1, T2, max_dist, max_angle, max_iter, fixed_iters, errs + p, iters ? iters + p : nullptr ) ) ) return rc;
       continue;
     }
@@ -1427,7 +1490,7 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
       return icp_align_multi_group( sources, target, T1s, n, T2, max_dist, max_angle, max_iter, fixed_iters, errs, iters, cls == 1 );
     std::vector<const rs_hip_cloud_t*> src( g.size() ); std::vector<float> T( 16 * g.size() ), e( g.size() ); std::vector<int32_t> it( g.size() );
     for( size_t k = 0; k < g.size(); ++k ) { src[k] = sources[g[k]]; std::memcpy( T.data() + 16 * k, T1s + 16 * g[k], 64 ); }
-    if( ( rc = icp_align_multi_group( src.data(), target, T.data(), (int)g.size(), T2, max_dist, max_angle, max_iter, fixed_iters, e.data(), it.data(), cls == 1 ) ) ) return rc;
+    { TrMap tm( g.data() ); if( ( rc = icp_align_multi_group( src.data(), target, T.data(), (int)g.size(), T2, max_dist, max_angle, max_iter, fixed_iters, e.data(), it.data(), cls == 1 ) ) ) return rc; }
     for( size_t k = 0; k < g.size(); ++k ) { std::memcpy( T1s + 16 * g[k], T.data() + 16 * k, 64 ); errs[g[k]] = e[k]; if( iters ) iters[g[k]] = it[k]; }
   }
   return RS_HIP_OK;
@@ -1440,6 +1503,7 @@ static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs
   int rc;
   IcpCtx cx;
   if( ( rc = icp_prepare( cx, nullptr, target, n, T2, sources ) ) ) return rc;
+  tr_clear( n );
   const float tmin = icp_gate_threshold( max_angle );
   if( ( rc = icp_enable_certificates( cx ) ) ) return rc;
   if( ( rc = icp_upload_state( cx, T1s, (size_t)n ) ) ) return rc;
@@ -1477,9 +1541,10 @@ static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs
   cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
   if( ( rc = icp_fills_flush() ) ) return rc;
   ProfChain prof;
+  std::vector<char> was_active( g_tr.kinds ? np : 0, 1 );
   for( int i = 0; i < max_iter; )                                       // icp.h:444
   {
-    const int chunk = g_icp_trace ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
+    const int chunk = ( g_icp_trace || g_tr.kinds ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
     for( int c = 0; c < chunk; ++c, ++i )
     {
       icp_set_radius( cx, max_dist, tmin );
@@ -1503,6 +1568,7 @@ static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs
     HIP_TRY( hipMemcpyAsync( hS, g_ws.state.p, state_bytes, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
     HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
     if( g_icp_trace && n == 1 && i >= 1 && i - 1 < g_icp_trace_cap ) g_icp_trace[i - 1] = hS[np * 34];      // the error after iteration i - 1
+    if( g_tr.kinds ) tr_record( n, i - 1, lane ? RS_HIP_ICP_STEP_LANE_CHAINS : RS_HIP_ICP_STEP_REF_ORDER, hS, was_active );
     int n_active = 0;
     for( int p = 0; p < n; ++p ) n_active += hActive[p] ? 1 : 0;
     if( n_active == 0 ) break;
@@ -1518,7 +1584,8 @@ static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs
     for( int q : edge )
     {
       std::memcpy( T1s + 16 * (size_t)q, T_in.data() + 16 * (size_t)q, 64 );
-      if( ( rc = icp_align_batch_impl( sources[q], target, T1s + 16 * (size_t)q, 1, T2, max_dist_in, max_angle, max_iter, fixed_iters, errs + q, iters ? iters + q : nullptr, 1, true ) ) ) return rc;
+      { TrShift ts( q ); if( ( rc = icp_align_batch_impl( sources[q], target, T1s + 16 * (size_t)q, 1, T2, max_dist_in, max_angle, max_iter, fixed_iters, errs + q, iters ? iters + q : nullptr, 1, true ) ) ) return rc; }
+      tr_mark_redone( q );
       g_stop_guard_redone.fetch_add( 1 );
     }
   }
@@ -1613,6 +1680,20 @@ int rs_hip_icp_align_traced( const rs_hip_cloud_t* source, const rs_hip_cloud_t*
   const int rc = rs_hip_icp_align( source, target, T1, T2, max_dist, max_angle, max_iter, fixed_iters, err, n_iters );
   g_icp_trace = nullptr; g_icp_trace_cap = 0;
   return rc;
+}
+
+int rs_hip_icp_trace_begin( float* poses, float* errs, int32_t* kinds, int32_t* redone, int32_t max_iter, int32_t n_problems )
+{
+  if( !poses || !errs || !kinds || !redone || max_iter < 1 || n_problems < 1 ) { set_err( "icp_trace_begin: bad arguments" ); return RS_HIP_E_ARG; }
+  g_tr.poses = poses; g_tr.errs = errs; g_tr.kinds = kinds; g_tr.redone = redone; g_tr.max_iter = max_iter; g_tr.n_prob = n_problems;
+  for( int g = 0; g < n_problems; ++g ) { tr_clear_row( g ); redone[g] = 0; }
+  return RS_HIP_OK;
+}
+
+int rs_hip_icp_trace_end( void )
+{
+  g_tr = IcpStepTrace{};
+  return RS_HIP_OK;
 }
 
 int rs_hip_icp_align( const rs_hip_cloud_t* source, const rs_hip_cloud_t* target,

@@ -158,3 +158,29 @@ def test_graft_entry_build():
     g.build()
     assert os.path.exists(os.path.join(ROOT, "rescan_amd", "librescan_hip.so"))
     assert os.path.exists(os.path.join(ROOT, "oracle", "librs_oracle.so"))
+
+
+def test_icp_batch_entry_points_validate_arguments_first(lib):
+    """rs_hip_icp_align_batch / _multi and rs_hip_icp_trace_begin reject null arrays and negative counts with RS_HIP_E_ARG
+    before they read anything (the batch used to copy its start poses through T1s first) — and without a device.  In a
+    child process: a regression would read through a null pointer."""
+    code = r"""
+import ctypes as C, sys
+lib = C.CDLL(sys.argv[1])
+vp, i32, f = C.c_void_p, C.c_int32, C.c_float
+buf = (C.c_float * 64)(); ibuf = (C.c_int32 * 16)(); src = (C.c_void_p * 1)(1)
+for name in ("rs_hip_icp_align_batch", "rs_hip_icp_align_multi"):
+    fn = getattr(lib, name); fn.restype = C.c_int
+    fn.argtypes = [vp, vp, vp, i32, vp, f, f, i32, i32, vp, vp]
+    first = C.addressof(src) if name.endswith("multi") else None
+    assert fn(first, None, None, 1, buf, 0.1, 1.0, 10, 0, buf, ibuf) == -2, name                   # null T1s (and clouds)
+    assert fn(first, None, buf, -1, buf, 0.1, 1.0, 10, 0, buf, ibuf) == -2, name                   # n < 0
+    assert fn(None, None, buf, 1, None, 0.1, 1.0, 10, 0, None, ibuf) == -2, name                   # null T2 / errs
+tb = lib.rs_hip_icp_trace_begin; tb.restype = C.c_int; tb.argtypes = [vp, vp, vp, vp, i32, i32]
+assert tb(None, buf, ibuf, ibuf, 2, 1) == -2 and tb(buf, buf, ibuf, ibuf, 0, 1) == -2 and tb(buf, buf, ibuf, ibuf, 2, -3) == -2
+lib.rs_hip_icp_trace_end.restype = C.c_int
+assert lib.rs_hip_icp_trace_end() == 0
+print("ok")
+"""
+    out = subprocess.run([sys.executable, "-c", code, LIB], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.strip() == "ok", (out.returncode, out.stdout, out.stderr)

@@ -366,6 +366,7 @@ def test_more_headline_rooms_vs_reference(capi, bench_mod, seed):
               f"scores max abs {d_sc:.2e}, {int((sc == g['scores']).sum())} of {len(sc)} bit-identical")
         assert it == bench_mod.ICP_ITERS and d_fixed < POSE_TOL and abs(err - float(g["icp_err"])) < 1e-5
         assert d_stop < POSE_TOL, f"icp_align with the stop test: {d_stop:.3e} from the reference ({it2} vs {int(g['stop_iters'])} iterations)"
+        assert it2 == int(g["stop_iters"]), f"icp_align with the stop test: {it2} vs the reference's {int(g['stop_iters'])} iterations"
         assert d_sc < SCORE_TOL
         assert (res["order"] == g["order"]).all()
         assert "reference" in str(g["labels_source"])
@@ -420,6 +421,7 @@ def _check_room(capi, bench_mod, g, w, with_stop):
         d_stop = np.linalg.norm(T2.astype(np.float64) - g["stop_pose"].astype(np.float64))
         msg += f"; icp_align r {md:.3f}: {d_stop:.3e}, {it2} vs {int(g['stop_iters'])} iterations"
         assert d_stop < POSE_TOL, msg
+        assert it2 == int(g["stop_iters"]), msg
     sc = capi.alignment_scores(w["obj_score"], w["scan1"], w["score_poses"], 0.1, 64)
     d_sc = np.abs(sc.astype(np.float64) - g["scores"].astype(np.float64)).max()
     res = capi.arrangement_to_labels(w["scan1"], w["plc_poses"], [p["cloud"] for p in w["plc"]], [0] * len(w["plc"]),

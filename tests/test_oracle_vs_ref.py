@@ -299,3 +299,16 @@ def test_level_poisson_vs_reference(oracle):
             a = oracle.level_poisson(p, LEVEL_VOXEL[level], level_max_n_neigh(level))
             b = ref_level_poisson(p, level)
             assert len(a) == len(b) and (a == b).all()
+
+
+def test_weighted_centroid_is_the_reference_chain(oracle, ref):
+    """orc_weighted_centroid (what tests/icp_restate.py's fp32 centroid chains are checked against) is the reference's
+    icp__compute_weighted_centroid bit for bit: offset coordinates, weights with zeros, sums that change binade many times."""
+    rng = np.random.default_rng(7)
+    for n, off in ((1, 0.0), (37, 2.5), (4096, -1.25), (70_000, 3.0), (70_000, 0.0)):
+        p = (rng.normal(0, 1.5, (n, 3)) + off).astype(np.float32)
+        w = rng.uniform(0, 1, n).astype(np.float32)
+        w[rng.uniform(0, 1, n) < 0.1] = 0.0
+        if n == 1:
+            w[:] = 0.5
+        assert oracle.weighted_centroid(p, w).tobytes() == ref.weighted_centroid(p, w).tobytes()
