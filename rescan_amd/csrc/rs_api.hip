@@ -152,11 +152,17 @@ void tr_clear_row( int g )
 }
 // a call starts over for its problems 0 .. n-1: whatever an earlier attempt left in their rows goes
 void tr_clear( int n ) { if( g_tr.kinds ) for( int p = 0; p < n; ++p ) { const int g = tr_global( p ); if( g >= 0 ) tr_clear_row( g ); } }
+// The ICP loop's device-resident state, one 4-byte word array after the other (n = n_prob); array X starts at word ICP_ST_X * n:
+//   T1 16n | active n | T1_prev 16n | iters n | err n | prev_err n | queued n | ticket 2n
+// ticket[0..n) carries the stop guard's flags: [p] = 1 when a stop test of problem p came within L.stop_guard of its threshold
+// (k_icp_update); the other n words stay zero.
+enum : size_t { ICP_ST_T1 = 0, ICP_ST_ACTIVE = 16, ICP_ST_T1_PREV = 17, ICP_ST_ITERS = 33, ICP_ST_ERR = 34, ICP_ST_PREV_ERR = 35,
+                ICP_ST_QUEUED = 36, ICP_ST_TICKET = 37, ICP_STATE_WORDS = 39 };
 // iteration i has just run for every problem with was_active[p]: its pose and error as the state holds them now (hS: the n-problem state)
 void tr_record( int n, int i, int kind, const float* hS, std::vector<char>& was_active )
 {
   const size_t np = (size_t)n;
-  const int* hActive = (const int*)( hS + np * 16 );
+  const int* hActive = (const int*)( hS + np * ICP_ST_ACTIVE );
   for( int p = 0; p < n; ++p )
   {
     if( !was_active[p] ) continue;
@@ -164,7 +170,7 @@ void tr_record( int n, int i, int kind, const float* hS, std::vector<char>& was_
     const int g = tr_global( p );
     if( g < 0 || i >= g_tr.max_iter ) continue;
     const size_t r = (size_t)g * g_tr.max_iter + i;
-    std::memcpy( g_tr.poses + r * 16, hS + 16 * p, 64 ); g_tr.errs[r] = hS[np * 34 + p]; g_tr.kinds[r] = kind;
+    std::memcpy( g_tr.poses + r * 16, hS + np * ICP_ST_T1 + 16 * p, 64 ); g_tr.errs[r] = hS[np * ICP_ST_ERR + p]; g_tr.kinds[r] = kind;
   }
 }
 void tr_mark_redone( int p ) { if( g_tr.redone ) { const int g = tr_global( p ); if( g >= 0 ) g_tr.redone[g] = 1; } }
@@ -201,11 +207,34 @@ std::atomic<int> g_lane_below{ getenv( "RS_HIP_LANE_CHAINS_BELOW" ) ? atoi( gete
 // 65 k 130 | 97); batches keep the lane chains up to g_lane_below (a walk per problem side by side: eight 50 k-point refines 20 us per
 // problem and iteration).  A threshold set beyond 65 536 (rs_hip_icp_lane_chains_below) means "the lane chains, whatever the call" and
 // holds for single calls too; any other setting caps them at 28 672.
-inline int lane_single_cap( int lane_below ) { return lane_below > 65536 ? lane_below : std::min( lane_below, 28672 ); }
-inline bool icp_takes_lane_chains( int n_source, int n_problems )
+// The two source sizes the policy is keyed on: object-sized sources (the sequential reference order of a bit-exact run, the lane chains'
+// default range; larger ones are scan-sized: early plain iterations) and the largest source with a bit-exact estimator (the replay).
+constexpr int ICP_OBJECT_PTS = 65536, ICP_EXACT_PTS = 262144;
+inline int lane_single_cap( int lane_below ) { return lane_below > ICP_OBJECT_PTS ? lane_below : std::min( lane_below, 28672 ); }
+// The estimators, by the RS_HIP_ICP_STEP_* code of their iterations (RS_HIP_ICP_STEP_PLAIN: the early iterations of GRID_CHAINS and
+// RECORDS, icp_plain_iterations).
+enum IcpEstimator
 {
+  ICP_EST_REF_ORDER   = RS_HIP_ICP_STEP_REF_ORDER,     // k_icp_faithful
+  ICP_EST_REPLAY      = RS_HIP_ICP_STEP_REPLAY,        // launch_icp_replay
+  ICP_EST_LANE_CHAINS = RS_HIP_ICP_STEP_LANE_CHAINS,   // launch_icp_lane_chains (object-sized: one wave per chain)
+  ICP_EST_GRID_CHAINS = RS_HIP_ICP_STEP_GRID_CHAINS,   // launch_icp_chain_centroids
+  ICP_EST_RECORDS     = RS_HIP_ICP_STEP_RECORDS,       // launch_icp_exact_centroids_from_records (centroid_mode 2: the cross-check, and a give-up's re-run)
+  ICP_EST_MOMENTS     = RS_HIP_ICP_STEP_MOMENTS,       // launch_icp_moments (centroid_mode 0)
+};
+struct IcpChoice { IcpEstimator est; bool guard; };
+// The estimator of a call of n_problems problems whose largest source has n_source points (centroid_mode: rs_hip_icp_exact_centroids;
+// force_bits: the reference's own order, sequential or parallel, whatever the thresholds say), and whether the stop test's guard
+// applies: only where the estimator is not the reference's order AND a bit-exact one exists to run the problem again with.
+IcpChoice icp_choose( int n_source, int n_problems, int centroid_mode, bool force_bits )
+{
+  if( n_source <= ( force_bits ? ICP_OBJECT_PTS : g_ref_order_below.load() ) ) return { ICP_EST_REF_ORDER, false };
+  if( n_source <= ( force_bits ? ICP_EXACT_PTS : g_replay_below.load() ) ) return { ICP_EST_REPLAY, false };
+  if( centroid_mode == 0 ) return { ICP_EST_MOMENTS, false };
   const int below = g_lane_below.load();
-  return n_source <= ( n_problems > 1 ? below : lane_single_cap( below ) );
+  const IcpEstimator est = n_source <= ( n_problems > 1 ? below : lane_single_cap( below ) ) ? ICP_EST_LANE_CHAINS
+                         : centroid_mode == 1 ? ICP_EST_GRID_CHAINS : ICP_EST_RECORDS;
+  return { est, n_source <= ICP_EXACT_PTS };
 }
 // The stop test's guard (round 6).  icp_align stops when |err - prev_err| < 1e-5 (icp.h:489).  The lane / grid chains follow the
 // reference's errors to 1e-8 ... 6e-7 (their moments are exact where the reference rounds): when a decisive difference passes within
@@ -235,9 +264,9 @@ inline int icp_plain_iterations( int n_source, int max_iter, bool fixed_iters )
   const int tail = std::max( 0, max_iter - keep );
   // (by SIZE, not by which kernels run the chains: an object refine contracts too slowly for this — rs_hip_icp_lane_chains_below( 0 ) puts
   //  50 k-point refines on the grid chains, and they keep them in every iteration)
-  if( n_source <= 65536 ) return 0;
+  if( n_source <= ICP_OBJECT_PTS ) return 0;
   if( fixed_iters ) return tail;
-  return n_source > 262144 ? std::min( std::max( 0, 7 - keep ), tail ) : 0;
+  return n_source > ICP_EXACT_PTS ? std::min( std::max( 0, 7 - keep ), tail ) : 0;
 }
 std::mutex g_prof_mutex;
 struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> spans; int64_t launches = 0; double ms = 0.0; };
@@ -817,10 +846,6 @@ struct IcpCtx
   size_t heavy_words = 0;      // words of one slow-tile buffer over all problems
 };
 
-// Device-resident loop state, one 4-byte word array after the other (n = n_prob):
-//   T1 16n | active n | T1_prev 16n | iters n | err n | prev_err n | queued n | ticket 2n
-constexpr size_t ICP_STATE_WORDS = 16 + 1 + 16 + 1 + 1 + 1 + 1 + 2;
-
 // One source for all problems (src), or one per problem (srcs[n_prob], src == null: a multi-source batch — the kernels then bind
 // their problem's view on the device, rs_icp.h: icp_bind).
 int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tgt, int n_prob, const float* T2, const rs_hip_cloud_t* const* srcs = nullptr )
@@ -882,8 +907,9 @@ int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tg
   static const int heavy_total = getenv( "RS_HIP_HEAVY_TOTAL" ) ? atoi( getenv( "RS_HIP_HEAVY_TOTAL" ) ) : 400;
   L.heavy_total = heavy_total;
   float* w = g_ws.state.as<float>();
-  L.T1 = w; L.active = (int*)( w + np * 16 ); L.T1_prev = w + np * 17;
-  L.iters = (int*)( w + np * 33 ); L.err = w + np * 34; L.prev_err = w + np * 35; L.queued = (int*)( w + np * 36 ); L.ticket = (int*)( w + np * 37 );
+  L.T1 = w + np * ICP_ST_T1; L.active = (int*)( w + np * ICP_ST_ACTIVE ); L.T1_prev = w + np * ICP_ST_T1_PREV;
+  L.iters = (int*)( w + np * ICP_ST_ITERS ); L.err = w + np * ICP_ST_ERR; L.prev_err = w + np * ICP_ST_PREV_ERR;
+  L.queued = (int*)( w + np * ICP_ST_QUEUED ); L.ticket = (int*)( w + np * ICP_ST_TICKET );
   L.solve = 0; L.iter_index = 0; L.fixed_iters = 0;
   L.seed = getenv( "RS_HIP_NO_SEED" ) ? 0 : 1;
   L.by_rows = getenv( "RS_HIP_NO_BY_ROWS" ) ? 0 : 1;
@@ -945,9 +971,9 @@ int icp_upload_state( IcpCtx& cx, const float* T1s, size_t np )
   int* hi = (int*)h;
   for( size_t p = 0; p < np; ++p )
   {
-    std::memcpy( h + 16 * p, T1s + 16 * p, 64 ); hi[np * 16 + p] = 1;
-    std::memcpy( h + np * 17 + 16 * p, T1s + 16 * p, 64 );
-    h[np * 34 + p] = 1e6f; h[np * 35 + p] = 1e6f;
+    std::memcpy( h + np * ICP_ST_T1 + 16 * p, T1s + 16 * p, 64 ); hi[np * ICP_ST_ACTIVE + p] = 1;
+    std::memcpy( h + np * ICP_ST_T1_PREV + 16 * p, T1s + 16 * p, 64 );
+    h[np * ICP_ST_ERR + p] = 1e6f; h[np * ICP_ST_PREV_ERR + p] = 1e6f;
   }
   HIP_TRY( hipMemcpyAsync( g_ws.state.p, h, np * ICP_STATE_WORDS * 4, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
   return RS_HIP_OK;
@@ -1067,20 +1093,14 @@ void icp_set_radius( IcpCtx& cx, float max_dist, float tmin )
   cx.L.stat_s2 = std::ldexp( 1.0, e2 ); cx.L.stat_i2 = std::ldexp( 1.0, -e2 );
 }
 
-} // namespace
-
-extern "C" {
-
-} // extern "C"
-
-namespace {
-// Buffers of the lane-chain estimator for n_prob problems with `rows` source points in all, the largest of max_n: the searches' records,
-// the seven totals per problem, the moments' partials (one per 1 024 source points of the largest problem), the update's ticket.
+// Buffers of the lane-chain estimator for the problems of cx (cx.total_pts source points in all, the largest cx.L.max_n): the searches'
+// records, the seven totals per problem, the moments' partials (one per 1 024 source points of the largest problem), the update's ticket.
 std::atomic<long long> g_lane_seq_addends{ 0 }, g_lane_addends{ 0 };      // (diagnostics: rs_hip_icp_lane_chains_sequential)
-int icp_lane_prepare( IcpCtx& cx, ChainBufs& CB, int n_prob, size_t rows, int max_n )
+int icp_lane_prepare( IcpCtx& cx, ChainBufs& CB )
 {
   int rc;
-  const size_t np = (size_t)n_prob;
+  const size_t np = (size_t)cx.L.n_prob, rows = cx.total_pts;
+  const int max_n = cx.L.max_n;
   CB.n_seg = chain_segments( max_n ); CB.n_blk = chain_blocks( max_n ); CB.refresh = 0;
   cx.L.n_mom_blocks = CB.n_blk * 4;
   if( ( rc = g_ws.ch_rec.ensure( std::max<size_t>( 1, rows ) * REC_F4 * 16 ) ) || ( rc = g_ws.rp_totals.ensure( np * 3 * ICP_NMOM * 8 ) ) ||
@@ -1121,70 +1141,51 @@ void icp_lane_account( const ChainBufs& CB, int n_prob )
   }
 }
 
-enum { ICP_CHAINS_GAVE_UP = -1000 };      // (internal) a centroid chain's walk gave the problem up: again, the seven sums by pass 2 of the replay
-
-enum { ICP_STOP_EDGE = -1001 };           // (internal) a stop test of some problem came within the guard of its threshold: *edge lists them
-
-int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* target,
-                          float* T1s, int32_t n, const float* T2, float max_dist, float max_angle,
-                          int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters, int centroid_mode,
-                          bool force_bits = false /* the reference's own order (sequential / parallel) whatever the thresholds say */,
-                          std::vector<int>* edge = nullptr /* out: problems whose stop test was decided inside the guard (their results are written all the same) */ )
+// One call's estimator: which (icp_choose), its buffers, its early plain iterations (icp_plain_iterations).
+struct IcpEst
 {
-  int rc = ensure_ready(); if( rc ) return rc;
-  if( !T1s || !T2 || !errs ) { set_err( "icp_align: null argument" ); return RS_HIP_E_ARG; }
-  IcpCtx cx;
-  if( ( rc = icp_prepare( cx, source, target, n, T2 ) ) ) return rc;
-  tr_clear( n );
-  const float tmin = icp_gate_threshold( max_angle );
-  if( source->n == 0 ) { for( int p = 0; p < n; ++p ) { errs[p] = 1e6f; if( iters ) iters[p] = 1; } return RS_HIP_OK; }   // n_corrs == 0 on the first search
-  if( ( rc = icp_enable_certificates( cx ) ) ) return rc;
-  if( ( rc = icp_upload_state( cx, T1s, (size_t)n ) ) ) return rc;
-  const bool ref_order = force_bits ? source->n <= 65536 : source->n <= g_ref_order_below.load();
-  const bool replay = !ref_order && ( force_bits ? source->n <= 262144 : source->n <= g_replay_below.load() );
-  const bool exact_centroids = !ref_order && !replay && centroid_mode != 0;
+  IcpEstimator est;
   ReplayBufs RB{};
   ChainBufs CB{};
-  const bool lane = exact_centroids && icp_takes_lane_chains( source->n, n );      // (object-sized: one wave per chain, launch_icp_lane_chains)
-  // the stop test's guard: only where the estimator is not the reference's order AND a bit-exact one exists to run the problem again with
-  cx.L.stop_guard = ( exact_centroids && !fixed_iters && edge && source->n <= 262144 ) ? g_stop_guard.load() : 0.0f;
-  const bool chains = exact_centroids && !lane && centroid_mode == 1;      // (2: the same sums through pass 2 of the replay — the cross-check, and what a problem the chains give up is run with)
-  // (2 reads the searches' records like the chains do — RS_HIP_REPLAY2_GATHER=1: from k_icp_faith_gather's arrays, as up to round 3)
-  static const bool replay2_gather = getenv( "RS_HIP_REPLAY2_GATHER" ) != nullptr;
-  const bool from_records = exact_centroids && !chains && !lane && !replay2_gather;
-  if( ref_order || replay || ( exact_centroids && !chains && !lane ) )
+  int n_plain = 0;
+};
+inline bool icp_exact_centroids( IcpEstimator e ) { return e == ICP_EST_LANE_CHAINS || e == ICP_EST_GRID_CHAINS || e == ICP_EST_RECORDS; }
+
+// The buffers of E.est for the problems of cx (cx.total_pts source points in all, the largest cx.L.max_n), their fills queued.
+int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
+{
+  int rc;
+  const int n = cx.L.n_prob, max_n = cx.L.max_n;
+  const size_t np = (size_t)n, pts = cx.total_pts;
+  ReplayBufs& RB = E.RB;
+  ChainBufs& CB = E.CB;
+  switch( E.est )
   {
-    if( !from_records )
-    {
-      if( ( rc = g_ws.faith.ensure( (size_t)n * FAITH_REC * (size_t)source->n * 4 ) ) ) return rc;
-      cx.L.faith = g_ws.faith.as<float>();
-    }
-    if( ( replay || exact_centroids ) && ( rc = replay_prepare( RB, n, source->n ) ) ) return rc;
-  }
-  if( chains )
-  {
-    if( ( rc = g_ws.rp_totals.ensure( (size_t)n * 3 * ICP_NMOM * 8 ) ) || ( rc = g_ws.rp_redone.ensure( (size_t)n * 4 + 64 ) ) ) return rc;
-    RB.totals = g_ws.rp_totals.as<double>(); RB.redone = g_ws.rp_redone.as<int>();
-    if( int rcf = icp_fill( g_ws.rp_redone.p, 0, (size_t)n * 4 + 64 ) ) return rcf;
-  }
-  if( lane )
-  {
-    if( ( rc = icp_lane_prepare( cx, CB, n, (size_t)n * (size_t)source->n, source->n ) ) ) return rc;
+  case ICP_EST_REF_ORDER:
+  case ICP_EST_REPLAY:
+    if( ( rc = g_ws.faith.ensure( (size_t)FAITH_REC * pts * 4 ) ) ) return rc;
+    cx.L.faith = g_ws.faith.as<float>();
+    if( E.est == ICP_EST_REPLAY && ( rc = replay_prepare( RB, n, max_n ) ) ) return rc;
+    return RS_HIP_OK;
+  case ICP_EST_LANE_CHAINS:
+    if( ( rc = icp_lane_prepare( cx, CB ) ) ) return rc;
     RB.totals = CB.totals;
-  }
-  if( exact_centroids ) { cx.L.exact_centroids = 1; cx.L.centroid_totals = RB.totals; }
-  if( chains )
+    break;
+  case ICP_EST_GRID_CHAINS:
   {
-    CB.n_seg = chain_segments( source->n ); CB.n_blk = chain_blocks( source->n );
-    const size_t rows = (size_t)n * CH_ROWS;
-    if( ( rc = g_ws.ch_rec.ensure( (size_t)n * (size_t)source->n * REC_F4 * 16 ) ) || ( rc = g_ws.ch_segsum.ensure( rows * CB.n_seg * 8 ) ) ||
+    if( ( rc = g_ws.rp_totals.ensure( np * 3 * ICP_NMOM * 8 ) ) || ( rc = g_ws.rp_redone.ensure( np * 4 + 64 ) ) ) return rc;
+    RB.totals = g_ws.rp_totals.as<double>(); RB.redone = g_ws.rp_redone.as<int>();
+    if( int rcf = icp_fill( g_ws.rp_redone.p, 0, np * 4 + 64 ) ) return rcf;
+    CB.n_seg = chain_segments( max_n ); CB.n_blk = chain_blocks( max_n );
+    const size_t rows = np * CH_ROWS;
+    if( ( rc = g_ws.ch_rec.ensure( pts * REC_F4 * 16 ) ) || ( rc = g_ws.ch_segsum.ensure( rows * CB.n_seg * 8 ) ) ||
         ( rc = g_ws.ch_prefix.ensure( rows * CB.n_blk * 4 * 8 ) ) || ( rc = g_ws.ch_seg.ensure( rows * CB.n_seg * sizeof( ChainRec ) ) ) ||
         ( rc = g_ws.ch_blk.ensure( rows * CB.n_blk * sizeof( ChainRec ) ) ) ||
         ( rc = g_ws.ch_guess.ensure( rows * CB.n_seg * 4 ) ) ) return rc;
     CB.segsum = g_ws.ch_segsum.as<double>(); CB.blksum = g_ws.ch_prefix.as<double>(); CB.seg = (ChainRec*)g_ws.ch_seg.p; CB.blk = (ChainRec*)g_ws.ch_blk.p; CB.guess = g_ws.ch_guess.as<int>();
     CB.totals = RB.totals; CB.resolved = RB.redone;
-    if( ( rc = g_ws.ch_done.ensure( (size_t)n * 8 ) ) ) return rc;
-    if( int rcf = icp_fill( g_ws.ch_done.p, 0, (size_t)n * 8 ) ) return rcf;
+    if( ( rc = g_ws.ch_done.ensure( np * 8 ) ) ) return rc;
+    if( int rcf = icp_fill( g_ws.ch_done.p, 0, np * 8 ) ) return rcf;
     CB.done = g_ws.ch_done.as<int>(); CB.failed = CB.done + n;
     if( getenv( "RS_HIP_CHAIN_DEBUG" ) )
     {
@@ -1201,121 +1202,69 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
     }
     cx.L.rec = (float4*)g_ws.ch_rec.p;
     cx.L.n_mom_blocks = CB.n_blk * 4;              // k_chain_moments: one workgroup, one partial, per quarter block (1 024 source points)
-    if( ( rc = g_ws.mom_part.ensure( (size_t)n * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
+    if( ( rc = g_ws.mom_part.ensure( np * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
     cx.L.mom_part = g_ws.mom_part.as<double>();
+    break;
   }
-  if( from_records )
-  {
-    // the searches' records, the chains' moment kernel and update (launch_icp_exact_centroids_from_records)
-    CB.n_seg = chain_segments( source->n ); CB.n_blk = chain_blocks( source->n ); CB.refresh = 0;
-    if( ( rc = g_ws.ch_rec.ensure( (size_t)n * (size_t)source->n * REC_F4 * 16 ) ) || ( rc = g_ws.ch_done.ensure( (size_t)n * 8 ) ) ||
-        ( rc = g_ws.mom_part.ensure( (size_t)n * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
-    if( int rcf = icp_fill( g_ws.ch_done.p, 0, (size_t)n * 8 ) ) return rcf;
+  case ICP_EST_RECORDS:
+    // the replay's buffers, the searches' records, the chains' moment kernel and update (launch_icp_exact_centroids_from_records)
+    if( ( rc = replay_prepare( RB, n, max_n ) ) ) return rc;
+    CB.n_seg = chain_segments( max_n ); CB.n_blk = chain_blocks( max_n ); CB.refresh = 0;
+    if( ( rc = g_ws.ch_rec.ensure( pts * REC_F4 * 16 ) ) || ( rc = g_ws.ch_done.ensure( np * 8 ) ) ||
+        ( rc = g_ws.mom_part.ensure( np * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
+    if( int rcf = icp_fill( g_ws.ch_done.p, 0, np * 8 ) ) return rcf;
     CB.done = g_ws.ch_done.as<int>();
     cx.L.rec = (float4*)g_ws.ch_rec.p;
     cx.L.n_mom_blocks = CB.n_blk * 4;
     cx.L.mom_part = g_ws.mom_part.as<double>();
+    break;
+  case ICP_EST_MOMENTS:
+    break;
   }
-  if( !ref_order && !replay )
-  {
-    if( int rcf = icp_fill( g_ws.stat_acc.p, 0, (size_t)n * STAT_SHARDS * 4 * 8 ) ) return rcf;
-    cx.L.stat_acc = g_ws.stat_acc.as<unsigned long long>();
-  }
-  const size_t heavy_words = cx.heavy_words;
-  const bool reorder = !getenv( "RS_HIP_NO_LPT" );
-  if( reorder )
-  {
-    if( ( rc = g_ws.order_a.ensure( heavy_words * 4 ) ) || ( rc = g_ws.order_b.ensure( heavy_words * 4 ) ) ) return rc;
-    if( int rcf = icp_fill( g_ws.order_a.p, 0, heavy_words * 4 ) ) return rcf;
-    if( int rcf = icp_fill( g_ws.order_b.p, 0, heavy_words * 4 ) ) return rcf;
-  }
+  if( icp_exact_centroids( E.est ) ) { cx.L.exact_centroids = 1; cx.L.centroid_totals = RB.totals; }
+  // (the fp64 moments' integer statistics)
+  if( int rcf = icp_fill( g_ws.stat_acc.p, 0, np * STAT_SHARDS * 4 * 8 ) ) return rcf;
+  cx.L.stat_acc = g_ws.stat_acc.as<unsigned long long>();
+  return RS_HIP_OK;
+}
 
-  // The whole iteration runs on the device (search, statistics, moments, solve, pose update, stop
-  // tests), so iterations are enqueued back to back and the host looks at the state only once per
-  // chunk; problems that stopped inside a chunk turn the rest of its launches into no-ops
-  // (every kernel returns at once for an inactive problem).
-  const bool debug = getenv( "RS_HIP_DEBUG" ) || getenv( "RS_HIP_DEBUG_CYCLES" );
-  static const int chunk_env = getenv( "RS_HIP_ICP_CHUNK" ) ? atoi( getenv( "RS_HIP_ICP_CHUNK" ) ) : 4;
-  const size_t np = (size_t)n, state_bytes = np * ICP_STATE_WORDS * 4;
-  float* hS = g_ws.h_b.as<float>();
-  const int* hActive = (const int*)( hS + np * 16 );
-  const long long total_tiles = (long long)cx.total_tiles;
-  static const long long coop_all_below = getenv( "RS_HIP_COOP_ALL_BELOW" ) ? atoll( getenv( "RS_HIP_COOP_ALL_BELOW" ) ) : 4096;
-  static const int coop_waves_forced = getenv( "RS_HIP_COOP_WAVES" ) ? atoi( getenv( "RS_HIP_COOP_WAVES" ) ) : 0;
+// Enqueues the estimator launches of iteration i; returns the RS_HIP_ICP_STEP_* kind of what it launched.
+int icp_step( IcpCtx& cx, IcpEst& E, int i )
+{
   static const int chain_refresh = std::max( 0, getenv( "RS_HIP_CHAIN_REFRESH" ) ? atoi( getenv( "RS_HIP_CHAIN_REFRESH" ) ) : 0 );
-  cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
-  // (see g_early_plain.  Scan-sized sources only: the eight 50 k-point refines of bench.py --scaling strong end 2.2e-6 from the reference with the
-  //  chains throughout, 8.7e-6 with three plain iterations, 2.0e-5 with seven or eight — an object refine contracts more slowly than a scan-to-scan fit)
-  const int n_plain = ( chains || from_records ) ? icp_plain_iterations( source->n, max_iter, fixed_iters != 0 ) : 0;
-  if( ( rc = icp_fills_flush() ) ) return rc;      // everything the call's first kernels expect zeroed, in one launch
-  ProfChain prof;
-  int kind = RS_HIP_ICP_STEP_NONE;                  // (rs_hip_icp_trace_begin: the estimator of the iteration just enqueued)
-  std::vector<char> was_active( g_tr.kinds ? np : 0, 1 );
-  for( int i = 0; i < max_iter; )                                       // icp.h:444
+  switch( E.est )
   {
-    // (the stop test looks at i > 5, icp.h:489: the first seven iterations go out in one piece, then chunk_env at a time — an iteration enqueued
-    //  behind the one that stopped is six empty launches, a look at the state a copy and a synchronisation)
-    const int chunk = ( debug || g_icp_trace || g_tr.kinds ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
-    for( int c = 0; c < chunk; ++c, ++i )
+  case ICP_EST_REF_ORDER:   launch_icp_faithful( cx.L, g_stream ); break;
+  case ICP_EST_REPLAY:      launch_icp_replay( cx.L, E.RB, g_stream ); break;
+  case ICP_EST_LANE_CHAINS: launch_icp_lane_chains( cx.L, E.CB, g_stream ); break;
+  case ICP_EST_MOMENTS:     launch_icp_moments( cx.L, g_stream ); break;
+  case ICP_EST_GRID_CHAINS:
+  case ICP_EST_RECORDS:
+    if( i < E.n_plain )
     {
-      icp_set_radius( cx, max_dist, tmin );
-      cx.L.iter_index = i;
-      cx.L.warm = ( i > 0 && !getenv( "RS_HIP_NO_WARM" ) ) ? 1 : 0;   // every active problem wrote m_slot in iteration i-1
-      // a short queue is bound by its heaviest tile: from the third iteration on the certificates have
-      // emptied it (small batches: always)
-      // launches of a few thousand tiles go straight to the cooperative kernel (launch_icp_corr); it is bound by its
-      // heaviest tile while the list is short (8 waves per tile), by throughput beyond (4)
-      cx.L.coop_all = total_tiles <= coop_all_below ? 1 : 0;
-      cx.L.coop_waves = icp_coop_waves( cx.L, total_tiles, n, i );
-      if( coop_waves_forced ) cx.L.coop_waves = coop_waves_forced;
-      if( reorder )
-      {
-        cx.L.heavy_in = i == 0 ? nullptr : ( ( i & 1 ) ? g_ws.order_a.as<int>() : g_ws.order_b.as<int>() );
-        cx.L.heavy_out = ( i & 1 ) ? g_ws.order_b.as<int>() : g_ws.order_a.as<int>();
-      }
-      if( debug ) icp_debug_before( cx, n );
-      prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
-      if( debug ) icp_debug_after( cx, source->n, n, i, max_dist );
-      prof.mark( "icp_moments" );
-      if( replay ) { launch_icp_replay( cx.L, RB, g_stream ); kind = RS_HIP_ICP_STEP_REPLAY; }
-      else if( chains )
-      {
-        // the binade guesses of the chains' records: made from the sums of the iteration before (k_chain_walk_and_moments) — in the first
-        // iteration from its own, so the records and the walks wait for the moments there (RS_HIP_CHAIN_REFRESH=k: in every k-th as well)
-        if( i < n_plain )
-        {
-          IcpLaunch Lp = cx.L; Lp.exact_centroids = 0;
-          launch_icp_plain_from_records( Lp, CB, g_stream ); kind = RS_HIP_ICP_STEP_PLAIN;
-        }
-        else
-        {
-          CB.refresh = ( i == n_plain || ( chain_refresh > 0 && ( i % chain_refresh ) == 0 ) ) ? 1 : 0;
-          launch_icp_chain_centroids( cx.L, CB, g_stream ); kind = RS_HIP_ICP_STEP_GRID_CHAINS;
-        }
-      }
-      else if( lane ) { launch_icp_lane_chains( cx.L, CB, g_stream ); kind = RS_HIP_ICP_STEP_LANE_CHAINS; }
-      else if( from_records && i < n_plain ) { IcpLaunch Lp = cx.L; Lp.exact_centroids = 0; launch_icp_plain_from_records( Lp, CB, g_stream ); kind = RS_HIP_ICP_STEP_PLAIN; }
-      else if( from_records ) { launch_icp_exact_centroids_from_records( cx.L, RB, CB, g_stream ); kind = RS_HIP_ICP_STEP_RECORDS; }
-      else if( exact_centroids ) { launch_icp_exact_centroids( cx.L, RB, g_stream ); kind = RS_HIP_ICP_STEP_RECORDS; }
-      else if( cx.L.faith ) { launch_icp_faithful( cx.L, g_stream ); kind = RS_HIP_ICP_STEP_REF_ORDER; }
-      else { launch_icp_moments( cx.L, g_stream ); kind = RS_HIP_ICP_STEP_MOMENTS; }
-      double nd = max_dist * 0.95;                                      // icp.h:493
-      max_dist = (float)( nd > 0.05 ? nd : 0.05 );
+      IcpLaunch Lp = cx.L; Lp.exact_centroids = 0;
+      launch_icp_plain_from_records( Lp, E.CB, g_stream );
+      return RS_HIP_ICP_STEP_PLAIN;
     }
-    prof.mark( nullptr );
-    HIP_TRY( hipMemcpyAsync( hS, g_ws.state.p, state_bytes, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
-    HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
-    if( g_icp_trace && n == 1 && i >= 1 && i - 1 < g_icp_trace_cap ) g_icp_trace[i - 1] = hS[np * 34];      // the error after iteration i - 1
-    if( g_tr.kinds ) tr_record( n, i - 1, kind, hS, was_active );
-    int n_active = 0;
-    for( int p = 0; p < n; ++p ) n_active += hActive[p] ? 1 : 0;
-    if( n_active == 0 ) break;
+    if( E.est == ICP_EST_RECORDS ) { launch_icp_exact_centroids_from_records( cx.L, E.RB, E.CB, g_stream ); break; }
+    // the binade guesses of the chains' records: made from the sums of the iteration before (k_chain_walk_and_moments) — in the first
+    // chain iteration from its own, so the records and the walks wait for the moments there (RS_HIP_CHAIN_REFRESH=k: in every k-th as well)
+    E.CB.refresh = ( i == E.n_plain || ( chain_refresh > 0 && ( i % chain_refresh ) == 0 ) ) ? 1 : 0;
+    launch_icp_chain_centroids( cx.L, E.CB, g_stream );
+    break;
   }
-  if( lane ) icp_lane_account( CB, n );
-  if( exact_centroids && getenv( "RS_HIP_DEBUG_TOTALS" ) )      // the seven centroid sums of the last iteration, as the estimator used them (bits)
+  return E.est;
+}
+
+// (diagnostics after the loop of a one-source call) RS_HIP_DEBUG_TOTALS: the seven centroid sums of the last iteration, as the estimator
+// used them (bits); RS_HIP_CHAIN_DEBUG: which segments the last iteration's chain walks added up addend by addend, and why their record
+// did not fit, then — unless the chains gave the call up — the walks' self-check.
+void icp_debug_report( const IcpEst& E, int n, int centroid_mode, bool gave_up )
+{
+  if( icp_exact_centroids( E.est ) && getenv( "RS_HIP_DEBUG_TOTALS" ) )
   {
     std::vector<double> t( (size_t)n * 3 * ICP_NMOM );
-    (void)hipMemcpy( t.data(), RB.totals, t.size() * 8, hipMemcpyDeviceToHost );
+    (void)hipMemcpy( t.data(), E.RB.totals, t.size() * 8, hipMemcpyDeviceToHost );
     for( int p = 0; p < n; ++p )
     {
       fprintf( stderr, "[rs_hip totals] mode %d problem %d:", centroid_mode, p );
@@ -1323,10 +1272,10 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
       fprintf( stderr, "\n" );
     }
   }
-  if( CB.dbg )      // RS_HIP_CHAIN_DEBUG: which segments the last iteration's chain walks added up addend by addend, and why their record did not fit
+  if( E.CB.dbg )
   {
     std::vector<int> d( (size_t)CH_ROWS * ( 4 + 64 * 8 ) );
-    (void)hipMemcpy( d.data(), CB.dbg, d.size() * 4, hipMemcpyDeviceToHost );
+    (void)hipMemcpy( d.data(), E.CB.dbg, d.size() * 4, hipMemcpyDeviceToHost );
     for( int r = 0; r < CH_ROWS; ++r )
     {
       const int* q = d.data() + (size_t)r * ( 4 + 64 * 8 );
@@ -1346,16 +1295,10 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
       }
     }
   }
-  if( chains )
-  {
-    std::vector<int> failed( (size_t)n );
-    HIP_TRY( hipMemcpy( failed.data(), CB.failed, (size_t)n * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
-    for( int p = 0; p < n; ++p ) if( failed[p] ) { g_chains_gave_up.fetch_add( 1 ); return ICP_CHAINS_GAVE_UP; }      // (nothing written to the caller's arrays yet)
-  }
-  if( CB.chk )
+  if( E.CB.chk && !gave_up )
   {
     std::vector<int> c( (size_t)CH_ROWS * ( 4 + 3 * 4096 ) );
-    (void)hipMemcpy( c.data(), CB.chk, c.size() * 4, hipMemcpyDeviceToHost );
+    (void)hipMemcpy( c.data(), E.CB.chk, c.size() * 4, hipMemcpyDeviceToHost );
     for( int r = 0; r < CH_ROWS; ++r )
     {
       const int* q = c.data() + (size_t)r * ( 4 + 3 * 4096 );
@@ -1367,13 +1310,139 @@ int icp_align_batch_impl( const rs_hip_cloud_t* source, const rs_hip_cloud_t* ta
       show( k );
     }
   }
-  const int* hIters = (const int*)( hS + np * 33 );
-  for( int p = 0; p < n; ++p ) { std::memcpy( T1s + 16 * p, hS + 16 * p, 64 ); errs[p] = hS[np * 34 + p]; if( iters ) iters[p] = hIters[p]; }
-  if( edge && cx.L.stop_guard > 0.0f )
+}
+
+enum { ICP_CHAINS_GAVE_UP = -1000 };      // (internal) a centroid chain's walk gave the problem up: again, the seven sums by pass 2 of the replay
+
+enum { ICP_STOP_EDGE = -1001 };           // (internal) a stop test of some problem came within the guard of its threshold: *edge lists them
+
+// the problems whose stop test was decided inside the guard, with their start poses (16 floats each, in the order of p)
+struct StopEdges { std::vector<int> p; std::vector<float> T_in; };
+
+// One ICP call for n problems: one source for all (src), or one per problem (srcs[n], src == null: a multi-source
+// batch — the reference-order and lane-chain estimators only, see rs_hip_icp_align_multi).  Writes T1s, errs and iters, except when a
+// grid chain gave a problem up (ICP_CHAINS_GAVE_UP: nothing written yet).  With the stop test and the guard armed (icp_choose), the
+// problems decided inside the guard go to *edge and ICP_STOP_EDGE comes back; their results are written all the same.
+int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs, const rs_hip_cloud_t* target,
+                    float* T1s, int32_t n, const float* T2, float max_dist, float max_angle,
+                    int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters, int centroid_mode,
+                    bool force_bits /* the reference's own order (sequential / parallel) whatever the thresholds say */, StopEdges* edge )
+{
+  int rc = ensure_ready(); if( rc ) return rc;
+  if( !T1s || !T2 || !errs ) { set_err( "icp_align: null argument" ); return RS_HIP_E_ARG; }
+  IcpCtx cx;
+  if( ( rc = icp_prepare( cx, src, target, n, T2, srcs ) ) ) return rc;
+  tr_clear( n );
+  const float tmin = icp_gate_threshold( max_angle );
+  if( src && src->n == 0 ) { for( int p = 0; p < n; ++p ) { errs[p] = 1e6f; if( iters ) iters[p] = 1; } return RS_HIP_OK; }   // n_corrs == 0 on the first search
+  if( ( rc = icp_enable_certificates( cx ) ) ) return rc;
+  if( ( rc = icp_upload_state( cx, T1s, (size_t)n ) ) ) return rc;
+  const IcpChoice choice = icp_choose( cx.L.max_n, n, centroid_mode, force_bits );
+  // (the other estimators' kernels are built for one source per launch)
+  if( srcs && choice.est != ICP_EST_REF_ORDER && choice.est != ICP_EST_LANE_CHAINS ) { set_err( "icp_align_multi: the estimator thresholds changed during the call" ); return RS_HIP_E_ARG; }
+  IcpEst E{ choice.est };
+  if( ( rc = icp_estimator_prepare( cx, E ) ) ) return rc;
+  // (see g_early_plain.  Scan-sized sources only: the eight 50 k-point refines of bench.py --scaling strong end 2.2e-6 from the reference with the
+  //  chains throughout, 8.7e-6 with three plain iterations, 2.0e-5 with seven or eight — an object refine contracts more slowly than a scan-to-scan fit)
+  if( E.est == ICP_EST_GRID_CHAINS || E.est == ICP_EST_RECORDS ) E.n_plain = icp_plain_iterations( cx.L.max_n, max_iter, fixed_iters != 0 );
+  cx.L.stop_guard = ( choice.guard && !fixed_iters && edge ) ? g_stop_guard.load() : 0.0f;
+  const size_t heavy_words = cx.heavy_words;
+  const bool reorder = !getenv( "RS_HIP_NO_LPT" );
+  if( reorder )
   {
-    const int* hEdge = (const int*)( hS + np * 37 );
-    for( int p = 0; p < n; ++p ) if( hEdge[p] ) edge->push_back( p );
-    if( !edge->empty() ) return ICP_STOP_EDGE;
+    if( ( rc = g_ws.order_a.ensure( heavy_words * 4 ) ) || ( rc = g_ws.order_b.ensure( heavy_words * 4 ) ) ) return rc;
+    if( int rcf = icp_fill( g_ws.order_a.p, 0, heavy_words * 4 ) ) return rcf;
+    if( int rcf = icp_fill( g_ws.order_b.p, 0, heavy_words * 4 ) ) return rcf;
+  }
+
+  // The whole iteration runs on the device (search, statistics, moments, solve, pose update, stop
+  // tests), so iterations are enqueued back to back and the host looks at the state only once per
+  // chunk; problems that stopped inside a chunk turn the rest of its launches into no-ops
+  // (every kernel returns at once for an inactive problem).
+  const bool debug = !srcs && ( getenv( "RS_HIP_DEBUG" ) || getenv( "RS_HIP_DEBUG_CYCLES" ) );
+  static const int chunk_env = getenv( "RS_HIP_ICP_CHUNK" ) ? atoi( getenv( "RS_HIP_ICP_CHUNK" ) ) : 4;
+  const size_t np = (size_t)n, state_bytes = np * ICP_STATE_WORDS * 4;
+  float* hS = g_ws.h_b.as<float>();
+  const int* hActive = (const int*)( hS + np * ICP_ST_ACTIVE );
+  const long long total_tiles = (long long)cx.total_tiles;
+  static const long long coop_all_below = getenv( "RS_HIP_COOP_ALL_BELOW" ) ? atoll( getenv( "RS_HIP_COOP_ALL_BELOW" ) ) : 4096;
+  static const int coop_waves_forced = getenv( "RS_HIP_COOP_WAVES" ) ? atoi( getenv( "RS_HIP_COOP_WAVES" ) ) : 0;
+  cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
+  if( ( rc = icp_fills_flush() ) ) return rc;      // everything the call's first kernels expect zeroed, in one launch
+  ProfChain prof;
+  int kind = RS_HIP_ICP_STEP_NONE;                  // (rs_hip_icp_trace_begin: the estimator of the iteration just enqueued)
+  std::vector<char> was_active( g_tr.kinds ? np : 0, 1 );
+  for( int i = 0; i < max_iter; )                                       // icp.h:444
+  {
+    // (the stop test looks at i > 5, icp.h:489: the first seven iterations go out in one piece, then chunk_env at a time — an iteration enqueued
+    //  behind the one that stopped is six empty launches, a look at the state a copy and a synchronisation)
+    const int chunk = ( debug || g_icp_trace || g_tr.kinds ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
+    for( int c = 0; c < chunk; ++c, ++i )
+    {
+      icp_set_radius( cx, max_dist, tmin );
+      cx.L.iter_index = i;
+      cx.L.warm = ( i > 0 && !getenv( "RS_HIP_NO_WARM" ) ) ? 1 : 0;   // every active problem wrote m_slot in iteration i-1
+      // launches of a few thousand tiles go straight to the cooperative kernel (launch_icp_corr); it is bound by its
+      // heaviest tile while the list is short (8 waves per tile), by throughput beyond (4)
+      cx.L.coop_all = total_tiles <= coop_all_below ? 1 : 0;
+      cx.L.coop_waves = icp_coop_waves( cx.L, total_tiles, n, i );
+      if( coop_waves_forced ) cx.L.coop_waves = coop_waves_forced;
+      if( reorder )
+      {
+        cx.L.heavy_in = i == 0 ? nullptr : ( ( i & 1 ) ? g_ws.order_a.as<int>() : g_ws.order_b.as<int>() );
+        cx.L.heavy_out = ( i & 1 ) ? g_ws.order_b.as<int>() : g_ws.order_a.as<int>();
+      }
+      if( debug ) icp_debug_before( cx, n );
+      prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
+      if( debug ) icp_debug_after( cx, cx.L.max_n, n, i, max_dist );
+      prof.mark( "icp_moments" ); kind = icp_step( cx, E, i );
+      double nd = max_dist * 0.95;                                      // icp.h:493
+      max_dist = (float)( nd > 0.05 ? nd : 0.05 );
+    }
+    prof.mark( nullptr );
+    HIP_TRY( hipMemcpyAsync( hS, g_ws.state.p, state_bytes, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
+    HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
+    if( g_icp_trace && n == 1 && i >= 1 && i - 1 < g_icp_trace_cap ) g_icp_trace[i - 1] = hS[np * ICP_ST_ERR];      // the error after iteration i - 1
+    if( g_tr.kinds ) tr_record( n, i - 1, kind, hS, was_active );
+    int n_active = 0;
+    for( int p = 0; p < n; ++p ) n_active += hActive[p] ? 1 : 0;
+    if( n_active == 0 ) break;
+  }
+  if( E.est == ICP_EST_LANE_CHAINS ) icp_lane_account( E.CB, n );
+  bool gave_up = false;
+  if( E.est == ICP_EST_GRID_CHAINS )
+  {
+    std::vector<int> failed( np );
+    HIP_TRY( hipMemcpy( failed.data(), E.CB.failed, np * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+    for( int p = 0; p < n; ++p ) gave_up = gave_up || failed[p] != 0;
+  }
+  if( !srcs ) icp_debug_report( E, n, centroid_mode, gave_up );
+  if( gave_up ) { g_chains_gave_up.fetch_add( 1 ); return ICP_CHAINS_GAVE_UP; }      // (nothing written to the caller's arrays yet)
+  const int* hIters = (const int*)( hS + np * ICP_ST_ITERS );
+  const int* hEdge = (const int*)( hS + np * ICP_ST_TICKET );
+  const bool guarded = edge && cx.L.stop_guard > 0.0f;
+  for( int p = 0; p < n; ++p )
+  {
+    if( guarded && hEdge[p] ) { edge->p.push_back( p ); edge->T_in.insert( edge->T_in.end(), T1s + 16 * p, T1s + 16 * p + 16 ); }   // (its start pose, still there)
+    std::memcpy( T1s + 16 * p, hS + np * ICP_ST_T1 + 16 * p, 64 ); errs[p] = hS[np * ICP_ST_ERR + p]; if( iters ) iters[p] = hIters[p];
+  }
+  return guarded && !edge->p.empty() ? ICP_STOP_EDGE : RS_HIP_OK;
+}
+
+// The stop guard's re-runs: every problem of `edge` again, alone, from its start pose and the caller's max_dist (the loop shrinks its own,
+// icp.h:493), in the reference's own order — its decisions, its bits.  Problem q's source: srcs ? srcs[q] : src.
+int icp_stop_guard_rerun( const StopEdges& edge, const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs, const rs_hip_cloud_t* target,
+                          float* T1s, const float* T2, float max_dist, float max_angle, int32_t max_iter, int32_t fixed_iters,
+                          float* errs, int32_t* iters, int centroid_mode )
+{
+  for( size_t k = 0; k < edge.p.size(); ++k )
+  {
+    const int q = edge.p[k];
+    float* T = T1s + 16 * (size_t)q;
+    std::memcpy( T, edge.T_in.data() + 16 * k, 64 );
+    { TrShift ts( q ); if( int rc = icp_align_impl( srcs ? srcs[q] : src, nullptr, target, T, 1, T2, max_dist, max_angle, max_iter, fixed_iters, errs + q, iters ? iters + q : nullptr, centroid_mode, true, nullptr ) ) return rc; }
+    tr_mark_redone( q );
+    g_stop_guard_redone.fetch_add( 1 );
   }
   return RS_HIP_OK;
 }
@@ -1405,32 +1474,16 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
     //  through the rest of the call: ~1.4 ms at a million points — is skipped; every 16th such call tries the chains again)
     int mode = g_exact_centroids.load();
     if( mode == 1 && per_point_records && g_chains_retry_after.load() > 0 && source->chains_wander.load() > 0 ) { source->chains_wander.fetch_sub( 1 ); mode = 2; }
-    // (the start poses are kept: a problem whose stop test falls inside the guard is run again from its own)
-    std::vector<float> T_in( T, T + 16 * (size_t)np );
-    std::vector<int> edge;
+    StopEdges edge;
     TrShift ts( p0 );
-    int rc = icp_align_batch_impl( source, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode, false, &edge );
+    int rc = icp_align_impl( source, nullptr, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode, false, &edge );
     // (a problem of the slice whose chains gave up: that slice again, its seven sums by pass 2 of the replay — nothing of it was written yet)
     if( rc == ICP_CHAINS_GAVE_UP )
     {
       source->chains_wander.store( g_chains_retry_after.load() );
-      edge.clear();
-      rc = icp_align_batch_impl( source, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, 2, false, &edge );
+      rc = icp_align_impl( source, nullptr, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, 2, false, &edge );
     }
-    if( rc == ICP_STOP_EDGE )
-    {
-      // those problems again, in the reference's own order: its decisions, its bits
-      for( int q : edge )
-      {
-        std::memcpy( T + 16 * (size_t)q, T_in.data() + 16 * (size_t)q, 64 );
-        int rc2;
-        { TrShift tq( q ); rc2 = icp_align_batch_impl( source, target, T + 16 * (size_t)q, 1, T2, max_dist, max_angle, max_iter, fixed_iters, e + q, it ? it + q : nullptr, mode, true ); }
-        if( rc2 ) return rc2;
-        tr_mark_redone( q );
-        g_stop_guard_redone.fetch_add( 1 );
-      }
-      rc = RS_HIP_OK;
-    }
+    if( rc == ICP_STOP_EDGE ) rc = icp_stop_guard_rerun( edge, source, nullptr, target, T, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode );
     if( rc ) return rc;
   }
   return RS_HIP_OK;
@@ -1442,18 +1495,6 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
 // their problem's source view on the device (rs_icp.h: icp_bind), so the sequential chains of all problems run side by side;
 // every problem's result is what rs_hip_icp_align returns for it alone, bit for bit.  A batch with a larger source is run
 // problem by problem (their estimators are built for one source per launch).
-// which estimator rs_hip_icp_align would give a source of n points: 0 the reference's order, 1 the lane chains, 2 anything else
-static int icp_estimator_class( int n )
-{
-  if( n <= g_ref_order_below.load() ) return 0;
-  if( n <= g_replay_below.load() ) return 2;
-  if( g_exact_centroids.load() != 0 && n <= g_lane_below.load() ) return 1;
-  return 2;
-}
-
-static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs_hip_cloud_t* target, float* T1s, int32_t n, const float* T2,
-                                  float max_dist, float max_angle, int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters, bool lane );
-
 int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_cloud_t* target,
                             float* T1s, int32_t n, const float* T2, float max_dist, float max_angle,
                             int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters )
@@ -1461,15 +1502,24 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
   if( !sources || !target || !T1s || !T2 || !errs || n < 0 ) { set_err( "icp_align_multi: bad arguments" ); return RS_HIP_E_ARG; }
   int rc = ensure_ready(); if( rc ) return rc;
   if( n == 0 ) return RS_HIP_OK;
-  // Every problem gets the estimator its own rs_hip_icp_align would (icp_estimator_class), so that its result is that call's bit for
-  // bit: the problems within the reference-order range run as one batch (k_icp_faithful), those within the lane chains' range as
-  // another (launch_icp_lane_chains), the rest — estimators built for one source per launch — one by one.
+  // Every problem gets the estimator its own rs_hip_icp_align would (icp_choose), so that its result is that call's bit for bit: the
+  // problems within the reference-order range run as one batch (k_icp_faithful), those within the lane chains' range as another
+  // (launch_icp_lane_chains), the rest — estimators built for one source per launch — one by one.
+  const int mode = g_exact_centroids.load();
   std::vector<int> group[3];
   for( int p = 0; p < n; ++p )
   {
     if( !sources[p] ) { set_err( "icp_align_multi: null source" ); return RS_HIP_E_ARG; }
-    group[sources[p]->n > 0 ? icp_estimator_class( sources[p]->n ) : 2].push_back( p );
+    const IcpEstimator est = icp_choose( sources[p]->n, n, mode, false ).est;
+    group[sources[p]->n <= 0 ? 2 : est == ICP_EST_REF_ORDER ? 0 : est == ICP_EST_LANE_CHAINS ? 1 : 2].push_back( p );
   }
+  // m >= 2 problems of one group in the same launches, then the stop guard's re-runs
+  auto run_group = [&]( const rs_hip_cloud_t* const* src, float* T, int m, float* e, int32_t* it )
+  {
+    StopEdges edge;
+    const int r = icp_align_impl( nullptr, src, target, T, m, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode, false, &edge );
+    return r == ICP_STOP_EDGE ? icp_stop_guard_rerun( edge, nullptr, src, target, T, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode ) : r;
+  };
   for( int p : group[2] )
   {
     TrShift ts( p );
@@ -1486,108 +1536,12 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
       if( ( rc = rs_hip_icp_align_batch( sources[p], target, T1s + 16 * p, 1, T2, max_dist, max_angle, max_iter, fixed_iters, errs + p, iters ? iters + p : nullptr ) ) ) return rc;
       continue;
     }
-    if( (int)g.size() == n )      // (the common case: one class, in place)
-      return icp_align_multi_group( sources, target, T1s, n, T2, max_dist, max_angle, max_iter, fixed_iters, errs, iters, cls == 1 );
+    if( (int)g.size() == n )      // (the common case: one group, in place)
+      return run_group( sources, T1s, n, errs, iters );
     std::vector<const rs_hip_cloud_t*> src( g.size() ); std::vector<float> T( 16 * g.size() ), e( g.size() ); std::vector<int32_t> it( g.size() );
     for( size_t k = 0; k < g.size(); ++k ) { src[k] = sources[g[k]]; std::memcpy( T.data() + 16 * k, T1s + 16 * g[k], 64 ); }
-    { TrMap tm( g.data() ); if( ( rc = icp_align_multi_group( src.data(), target, T.data(), (int)g.size(), T2, max_dist, max_angle, max_iter, fixed_iters, e.data(), it.data(), cls == 1 ) ) ) return rc; }
+    { TrMap tm( g.data() ); if( ( rc = run_group( src.data(), T.data(), (int)g.size(), e.data(), it.data() ) ) ) return rc; }
     for( size_t k = 0; k < g.size(); ++k ) { std::memcpy( T1s + 16 * g[k], T.data() + 16 * k, 64 ); errs[g[k]] = e[k]; if( iters ) iters[g[k]] = it[k]; }
-  }
-  return RS_HIP_OK;
-}
-
-// n >= 2 problems of ONE estimator class in the same launches: grid.y = problem, the kernels bind their problem's view on the device.
-static int icp_align_multi_group( const rs_hip_cloud_t* const* sources, const rs_hip_cloud_t* target, float* T1s, int32_t n, const float* T2,
-                                  float max_dist, float max_angle, int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters, bool lane )
-{
-  int rc;
-  IcpCtx cx;
-  if( ( rc = icp_prepare( cx, nullptr, target, n, T2, sources ) ) ) return rc;
-  tr_clear( n );
-  const float tmin = icp_gate_threshold( max_angle );
-  if( ( rc = icp_enable_certificates( cx ) ) ) return rc;
-  if( ( rc = icp_upload_state( cx, T1s, (size_t)n ) ) ) return rc;
-  ChainBufs CB{};
-  std::vector<float> T_in;
-  const float max_dist_in = max_dist;          // (the loop below shrinks max_dist, icp.h:493: a problem run again starts from the caller's)
-  if( lane )
-  {
-    if( ( rc = icp_lane_prepare( cx, CB, n, cx.total_pts, cx.L.max_n ) ) ) return rc;
-    cx.L.exact_centroids = 1; cx.L.centroid_totals = CB.totals;
-    if( !fixed_iters ) { cx.L.stop_guard = g_stop_guard.load(); T_in.assign( T1s, T1s + 16 * (size_t)n ); }      // (see icp_align_batch_impl)
-    if( int rcf = icp_fill( g_ws.stat_acc.p, 0, (size_t)n * STAT_SHARDS * 4 * 8 ) ) return rcf;
-    cx.L.stat_acc = g_ws.stat_acc.as<unsigned long long>();
-  }
-  else
-  {
-    if( ( rc = g_ws.faith.ensure( (size_t)FAITH_REC * cx.total_pts * 4 ) ) ) return rc;
-    cx.L.faith = g_ws.faith.as<float>();
-  }
-  const bool reorder = !getenv( "RS_HIP_NO_LPT" );
-  if( reorder )
-  {
-    if( ( rc = g_ws.order_a.ensure( cx.heavy_words * 4 ) ) || ( rc = g_ws.order_b.ensure( cx.heavy_words * 4 ) ) ) return rc;
-    if( int rcf = icp_fill( g_ws.order_a.p, 0, cx.heavy_words * 4 ) ) return rcf;
-    if( int rcf = icp_fill( g_ws.order_b.p, 0, cx.heavy_words * 4 ) ) return rcf;
-  }
-  // the loop of icp_align_batch_impl, reference-order estimator only
-  static const int chunk_env = getenv( "RS_HIP_ICP_CHUNK" ) ? atoi( getenv( "RS_HIP_ICP_CHUNK" ) ) : 4;
-  static const long long coop_all_below = getenv( "RS_HIP_COOP_ALL_BELOW" ) ? atoll( getenv( "RS_HIP_COOP_ALL_BELOW" ) ) : 4096;
-  static const int coop_waves_forced = getenv( "RS_HIP_COOP_WAVES" ) ? atoi( getenv( "RS_HIP_COOP_WAVES" ) ) : 0;
-  const size_t np = (size_t)n, state_bytes = np * ICP_STATE_WORDS * 4;
-  float* hS = g_ws.h_b.as<float>();
-  const int* hActive = (const int*)( hS + np * 16 );
-  const long long total_tiles = (long long)cx.total_tiles;
-  cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
-  if( ( rc = icp_fills_flush() ) ) return rc;
-  ProfChain prof;
-  std::vector<char> was_active( g_tr.kinds ? np : 0, 1 );
-  for( int i = 0; i < max_iter; )                                       // icp.h:444
-  {
-    const int chunk = ( g_icp_trace || g_tr.kinds ) ? 1 : ( fixed_iters ? max_iter - i : std::min( i == 0 ? std::max( 7, chunk_env ) : std::max( 1, chunk_env ), max_iter - i ) );
-    for( int c = 0; c < chunk; ++c, ++i )
-    {
-      icp_set_radius( cx, max_dist, tmin );
-      cx.L.iter_index = i;
-      cx.L.warm = ( i > 0 && !getenv( "RS_HIP_NO_WARM" ) ) ? 1 : 0;
-      cx.L.coop_all = total_tiles <= coop_all_below ? 1 : 0;
-      cx.L.coop_waves = icp_coop_waves( cx.L, total_tiles, n, i );
-      if( coop_waves_forced ) cx.L.coop_waves = coop_waves_forced;
-      if( reorder )
-      {
-        cx.L.heavy_in = i == 0 ? nullptr : ( ( i & 1 ) ? g_ws.order_a.as<int>() : g_ws.order_b.as<int>() );
-        cx.L.heavy_out = ( i & 1 ) ? g_ws.order_b.as<int>() : g_ws.order_a.as<int>();
-      }
-      prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
-      prof.mark( "icp_moments" );
-      if( lane ) launch_icp_lane_chains( cx.L, CB, g_stream ); else launch_icp_faithful( cx.L, g_stream );
-      double nd = max_dist * 0.95;                                      // icp.h:493
-      max_dist = (float)( nd > 0.05 ? nd : 0.05 );
-    }
-    prof.mark( nullptr );
-    HIP_TRY( hipMemcpyAsync( hS, g_ws.state.p, state_bytes, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
-    HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
-    if( g_icp_trace && n == 1 && i >= 1 && i - 1 < g_icp_trace_cap ) g_icp_trace[i - 1] = hS[np * 34];      // the error after iteration i - 1
-    if( g_tr.kinds ) tr_record( n, i - 1, lane ? RS_HIP_ICP_STEP_LANE_CHAINS : RS_HIP_ICP_STEP_REF_ORDER, hS, was_active );
-    int n_active = 0;
-    for( int p = 0; p < n; ++p ) n_active += hActive[p] ? 1 : 0;
-    if( n_active == 0 ) break;
-  }
-  if( lane ) icp_lane_account( CB, n );
-  const int* hIters = (const int*)( hS + np * 33 );
-  for( int p = 0; p < n; ++p ) { std::memcpy( T1s + 16 * p, hS + 16 * p, 64 ); errs[p] = hS[np * 34 + p]; if( iters ) iters[p] = hIters[p]; }
-  if( lane && cx.L.stop_guard > 0.0f )
-  {
-    // the problems whose stop test was decided inside the guard: again, each alone, in the reference's own order
-    std::vector<int> edge;
-    { const int* hEdge = (const int*)( hS + np * 37 ); for( int p = 0; p < n; ++p ) if( hEdge[p] ) edge.push_back( p ); }
-    for( int q : edge )
-    {
-      std::memcpy( T1s + 16 * (size_t)q, T_in.data() + 16 * (size_t)q, 64 );
-      { TrShift ts( q ); if( ( rc = icp_align_batch_impl( sources[q], target, T1s + 16 * (size_t)q, 1, T2, max_dist_in, max_angle, max_iter, fixed_iters, errs + q, iters ? iters + q : nullptr, 1, true ) ) ) return rc; }
-      tr_mark_redone( q );
-      g_stop_guard_redone.fetch_add( 1 );
-    }
   }
   return RS_HIP_OK;
 }

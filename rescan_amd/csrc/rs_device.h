@@ -136,7 +136,8 @@ struct IcpLaunch
   const int* by_orig;   // original source index -> query slot (null: identity)
   float*  faith;        // n_prob x FAITH_REC x nq: the correspondences in the source's own order
   // "exact centroids" estimator (large sources): the fp64 moments, but the seven sums behind the two weighted centroids
-  // (icp.h:136-148: Σw, Σw·p, Σw·q) as the reference's own sequential fp32 chains — see launch_icp_exact_centroids
+  // (icp.h:136-148: Σw, Σw·p, Σw·q) as the reference's own sequential fp32 chains — see launch_icp_chain_centroids, launch_icp_lane_chains
+  // and launch_icp_exact_centroids_from_records
   int     exact_centroids;
   const double* centroid_totals;   // n_prob x 3 x ICP_NMOM (ReplayBufs::totals): [ICP_NMOM + 0..6] = the seven chain totals
   // ... and their fast form (rs_icp_estimate.hip: "grid chains"): every search writes one 48-byte record per source point at the point's
@@ -192,8 +193,6 @@ struct ReplayBufs
   int*    redone;       // n_prob: segments re-added sequentially (diagnostics; may be null)
 };
 void   launch_icp_replay( const IcpLaunch& L, const ReplayBufs& B, hipStream_t st );
-// fp64 moments + the reference's own fp32 chains for Σw, Σw·p, Σw·q (pass 2 of the replay) + solve with those centroids
-void   launch_icp_exact_centroids( const IcpLaunch& L, const ReplayBufs& B, hipStream_t st );
 void   launch_icp_exact_centroids_from_records( const IcpLaunch& L, const ReplayBufs& B, const ChainBufs& C, hipStream_t st );
 int    replay_segments( int n_source );
 int    replay_superblocks( int n_source );

@@ -1171,15 +1171,6 @@ void launch_icp_replay( const IcpLaunch& L, const ReplayBufs& B, hipStream_t st 
   launch_replay_pass<3>( L, B, st );
   hipLaunchKernelGGL( k_replay_finish, dim3( L.n_prob ), dim3( WAVE ), 0, st, L, B );
 }
-// Large sources: k_icp_moments (parallel fp64) for everything but the two weighted centroids, whose seven sums run as the
-// reference's sequential fp32 chains (pass 2 of the replay, with the moments' own 2.5-sigma cut); k_icp_update centres on them.
-void launch_icp_exact_centroids( const IcpLaunch& L, const ReplayBufs& B, hipStream_t st )
-{
-  hipLaunchKernelGGL( k_icp_moments, dim3( L.n_mom_blocks, L.n_prob ), dim3( BLOCK ), 0, st, L );      // (also leaves n, mean, stddev in L.res)
-  hipLaunchKernelGGL( k_icp_faith_gather, dim3( ( L.src.n + BLOCK - 1 ) / BLOCK, L.n_prob ), dim3( BLOCK ), 0, st, L );
-  launch_replay_pass<2>( L, B, st );
-  hipLaunchKernelGGL( k_icp_update, dim3( L.n_prob ), dim3( UPDATE_WAVES * WAVE ), 0, st, L );
-}
 // ------------------------------------------------------------------------------------------
 // Grid chains: the reference's seven centroid sums (icp.h:136-148), bit for bit, at the cost of a reduction
 //
