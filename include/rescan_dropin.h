@@ -90,6 +90,18 @@ int   rsd_alignment_scores( const rsd_vec3_t* obj_pos, const rsd_vec3_t* obj_nor
                             const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn,
                             const rsd_mat4_t* xforms, int32_t n_poses, float search_radius, int32_t max_n_neigh,
                             float* scores );
+/* isect_get_overlap_factor (lib/rs/intersect.h:309-368) of two placed shapes, bit for bit: *_lvl1 = shape->positions[1] (the
+ * points that are rasterised), *_lvl3 = shape->positions[3] (the points whose boxes size the grid).  *overlap is written on
+ * success only (0; < 0: an RS_HIP_E_* code, see rs_hip_overlap_factors). */
+int   rsd_overlap_factor( const rsd_vec3_t* a_lvl1, int32_t a_n1, const rsd_vec3_t* a_lvl3, int32_t a_n3, const rsd_mat4_t* pose_a,
+                          const rsd_vec3_t* b_lvl1, int32_t b_n1, const rsd_vec3_t* b_lvl3, int32_t b_n3, const rsd_mat4_t* pose_b,
+                          float voxel_size, int voxelize_inside, int normalize_by_smaller, float* overlap );
+/* mgs_non_maxima_suppresion (apps/pose_proposal/pose_proposal.cpp:377-451) for ONE object's proposals: lvl1 / lvl3 as above,
+ * centroid = rs_pointcloud_centroid( shape, 0 ), poses[i] = proposals[i].xform, scores[i] = proposals[i].score.  marks[i] = 1
+ * keep / 2 discard; keep_idx[0 .. *n_keep) ascending: the caller copies proposals[keep_idx[k]] in that order (:441-447). */
+int   rsd_non_maxima_suppression( const rsd_vec3_t* lvl1, int32_t n1, const rsd_vec3_t* lvl3, int32_t n3, const rsd_vec3_t* centroid,
+                                  const rsd_mat4_t* poses, const float* scores, int32_t n, float dist_threshold,
+                                  int32_t* marks, int32_t* keep_idx, int32_t* n_keep );
 /* rspf_arrangement_to_labels' search part (lib/rs/rs_pointcloud_filters.cpp:796-848): placements in
  * arrangement order with per-placement static flag and class index; writes int8 labels (1-based
  * index into the sorted arrangement, whose permutation is returned in sorted_order). */

@@ -50,7 +50,7 @@ const char* rs_hip_version( void );
 /* Per-kernel timing with HIP events recorded on the launch stream.  While enabled, each
  * launch of a hot kernel is bracketed by an event pair; rs_hip_profile_read() synchronises
  * and returns launch count and summed milliseconds for kernel `name`
- * ("nn_icp", "icp_moments", "nn_score", "nn_label", "nn_rows", "edges", "coverage").  The name "candidates" is
+ * ("nn_icp", "icp_moments", "nn_score", "nn_label", "nn_rows", "edges", "coverage", "isect").  The name "candidates" is
  * not a kernel: its launch count is the number of candidates the search kernels staged and evaluated
  * since the last reset (each of them by the 64 query lanes of its wave) — SURVEY.md §8d's second figure. */
 int         rs_hip_profile_enable( int on );
@@ -418,6 +418,43 @@ int  rs_hip_coverage_scene_grid( const rs_hip_coverage_t* c, uint8_t* data );
 int  rs_hip_coverage_scores( rs_hip_coverage_t* c, const rs_hip_cloud_t* const* objects, const float* poses,
                              const int32_t* is_static, const int32_t* first_placement, int32_t n_arrangements,
                              float* scores, int32_t* agree );
+
+/* ---- voxel overlap of placed shapes, non-maximum suppression of pose proposals ---- */
+
+/* A shape is two device clouds of one object: its BOUNDARY cloud (the reference's level 1: the points that are rasterised,
+ * lib/rs/intersect.h:215) and its EXTENT cloud (level 3: the points whose transformed box sizes the grid, :114). */
+typedef struct rs_hip_isect_shape { const rs_hip_cloud_t* boundary; const rs_hip_cloud_t* extent; } rs_hip_isect_shape_t;
+
+/* isect_get_overlap_factor (lib/rs/intersect.h:309-368) for n_pairs pairs in one call, bit for bit: pair k places
+ * shapes[shape_a[k]] by poses_a[16k..] and shapes[shape_b[k]] by poses_b[16k..]; overlap[k] = cells occupied in both grids /
+ * max (normalize_by_smaller: min) of the two grids' occupied cells, 0 when the extent boxes do not intersect, 1 when that
+ * count is 0.  voxelize_inside = 0 counts boundary cells only (isect_compute_boundary_grid).  counts (may be NULL) =
+ * {count_a, count_b, both} per pair.  Refused, with nothing written: a pair whose grid has an x or z line of more than 4096
+ * cells while voxelize_inside is set — the reference's scanline arrays, :132-133 — or more than 2^20 cells along an axis or
+ * planes beyond 256 MB (RS_HIP_E_CAPACITY); a pair with a boundary point outside the grid of its extent boxes — the
+ * reference's assert, :227-229; impossible for a level pyramid, whose level 1 lies within 4 cm of level 3 and the grid is
+ * grown by 0.3 — (RS_HIP_E_ARG; rs_hip_last_error() names the pair). */
+int rs_hip_overlap_factors( const rs_hip_isect_shape_t* shapes, int32_t n_shapes,
+                            const int32_t* shape_a, const float* poses_a, const int32_t* shape_b, const float* poses_b,
+                            int32_t n_pairs, float voxel_size, int voxelize_inside, int normalize_by_smaller,
+                            float* overlap, int32_t* counts );
+
+/* mgs_non_maxima_suppresion for ONE object's proposals (apps/pose_proposal/pose_proposal.cpp:377-451): until every proposal
+ * is marked, the first unmarked proposal with the strictly largest score is kept, and every unmarked proposal i is discarded
+ * whose overlap with it (voxel 0.1, inside fill, normalised by the larger count) is > 0.5f, or whose transformed centroid lies
+ * closer than dist_threshold to the keep's, or whose score is < 0.01f.  centroid is rs_pointcloud_centroid( shape, 0 )
+ * (lib/rs/rs_pointcloud.h:1318-1340: a sequential fp64 sum over level 0, rounded to fp32): the caller's, like the reference's
+ * cached one.  marks[i] = 1 keep, 2 discard; keep_idx[0 .. *n_keep) ascending (:441-447); n_rounds (may be NULL) = rounds =
+ * keeps.  Scores that are NaN or <= -1e9 give RS_HIP_E_ARG (the reference would index with -1).  The rounds run on the host,
+ * one launch and one read-back of 12 bytes per evaluated pair each; the overlap is evaluated only where neither cheap test
+ * discards and the two extent boxes (computed once per proposal) intersect. */
+int rs_hip_nms( const rs_hip_isect_shape_t* shape, const float centroid[3], const float* poses, const float* scores, int32_t n,
+                float dist_threshold, int32_t* marks /* n: 1 keep, 2 discard */, int32_t* keep_idx, int32_t* n_keep, int32_t* n_rounds );
+/* (tests, diagnostics) Pairs whose four bit planes need at most `bytes` of LDS keep them there (default and maximum 61440); larger
+ * ones use a slab of global memory, same code, same bits.  0 sends every pair there; bytes < 0 only reads.  Returns the previous budget. */
+int32_t rs_hip_isect_lds_budget( int32_t bytes );
+/* (diagnostics) Pairs the process rasterised since the last reset, and pairs rs_hip_nms settled without (cheap tests, disjoint boxes). */
+void    rs_hip_isect_pairs( int64_t* evaluated, int64_t* skipped, int32_t reset );
 
 /* ---- host-side helpers shared by the drop-in shim (exact reference arithmetic) ------- */
 

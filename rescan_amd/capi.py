@@ -92,6 +92,12 @@ SIGNATURES = {
     "rs_hip_coverage_scores": (C.c_int, [C.c_void_p, C.c_void_p, f32p, i32p, i32p, C.c_int32, f32p, C.c_void_p]),
     "rs_hip_cloud_create_level": (C.c_void_p, [C.c_void_p, C.c_float, C.c_int32, C.c_float, i32p, C.POINTER(C.c_int32)]),
     "rs_hip_level_samples": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
+                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "rs_hip_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p]),
+    "rs_hip_isect_lds_budget": (C.c_int32, [C.c_int32]),
+    "rs_hip_isect_pairs": (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "rs_hip_mat4_inverse": (None, [f32p, f32p]),
     "rs_hip_sincosf_model": (None, [f32p, C.c_int64, f32p, f32p]),
     "rs_hip_mat4_mul": (None, [f32p, f32p, f32p]),
@@ -101,6 +107,11 @@ SIGNATURES = {
 
 class RescanHipError(RuntimeError):
     pass
+
+
+class IsectShape(C.Structure):
+    """rs_hip_isect_shape_t: (boundary cloud, extent cloud) of one object."""
+    _fields_ = [("boundary", C.c_void_p), ("extent", C.c_void_p)]
 
 
 class Placement(C.Structure):
@@ -670,3 +681,53 @@ class Coverage:
                 self.handle = None
         except Exception:
             pass
+
+
+def _isect_shapes(shapes):
+    arr = (IsectShape * len(shapes))()
+    for k, (b, e) in enumerate(shapes):
+        arr[k].boundary, arr[k].extent = b.handle, e.handle
+    return arr
+
+
+def overlap_factors(shapes, shape_a, poses_a, shape_b, poses_b, voxel_size=0.1, voxelize_inside=True, normalize_by_smaller=False):
+    """isect_get_overlap_factor for a batch of pairs (rs_hip_overlap_factors).  shapes: list of (boundary Cloud, extent Cloud);
+    pair k places shapes[shape_a[k]] by poses_a[k] and shapes[shape_b[k]] by poses_b[k].  Returns (overlap float32 [n],
+    counts int32 [n, 3] = count_a, count_b, both)."""
+    arr = _isect_shapes(shapes)
+    ia, ib = np.ascontiguousarray(shape_a, np.int32), np.ascontiguousarray(shape_b, np.int32)
+    pa, pb = _f32(poses_a).reshape(-1, 16), _f32(poses_b).reshape(-1, 16)
+    n = len(ia)
+    assert len(ib) == n and len(pa) == n and len(pb) == n
+    ov, cnt = np.zeros(n, np.float32), np.zeros((n, 3), np.int32)
+    _check(load().rs_hip_overlap_factors(C.addressof(arr), len(shapes), ia.ctypes.data, pa.ctypes.data, ib.ctypes.data, pb.ctypes.data, n,
+                                         float(np.float32(voxel_size)), int(bool(voxelize_inside)), int(bool(normalize_by_smaller)),
+                                         ov.ctypes.data, cnt.ctypes.data))
+    return ov, cnt
+
+
+def nms(shape, centroid, poses, scores, dist_threshold=0.2):
+    """mgs_non_maxima_suppresion of one object's proposals (rs_hip_nms).  shape: (boundary Cloud, extent Cloud); centroid: the
+    object's level-0 centroid as the reference caches it.  Returns (marks int32 [n]: 1 keep / 2 discard, keep_idx ascending, rounds)."""
+    arr = _isect_shapes([shape])
+    c = _f32(centroid).ravel()
+    p, s = _f32(poses).reshape(-1, 16), _f32(scores).ravel()
+    n = len(s)
+    assert len(p) == n and len(c) == 3
+    marks, keep = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    nk, nr = C.c_int32(), C.c_int32()
+    _check(load().rs_hip_nms(C.addressof(arr), c.ctypes.data, p.ctypes.data, s.ctypes.data, n, float(np.float32(dist_threshold)),
+                             marks.ctypes.data, keep.ctypes.data, C.addressof(nk), C.addressof(nr)))
+    return marks[:n], keep[:nk.value].copy(), nr.value
+
+
+def isect_lds_budget(nbytes=-1):
+    """Pairs whose bit planes fit `nbytes` of LDS keep them there, larger ones use global memory (0: all of them); returns the previous budget."""
+    return load().rs_hip_isect_lds_budget(int(nbytes))
+
+
+def isect_pairs(reset=False):
+    """(pairs rasterised, pairs rs_hip_nms settled without) since the last reset."""
+    a, b = C.c_int64(), C.c_int64()
+    load().rs_hip_isect_pairs(C.byref(a), C.byref(b), int(bool(reset)))
+    return a.value, b.value

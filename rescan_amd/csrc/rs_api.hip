@@ -2707,11 +2707,13 @@ extern "C" int rs_hip_coverage_scores( rs_hip_coverage_t* c, const rs_hip_cloud_
 }
 
 // ------------------------------------------------------------------------------------------
-// what the translation units with entry points of their own (rs_knn.hip) need from this one
+// what the translation units with entry points of their own (rs_knn.hip, rs_isect.hip) need from this one
 // ------------------------------------------------------------------------------------------
 
 namespace rs {
 int api_ready( hipStream_t* st ) { const int rc = ensure_ready(); if( rc == RS_HIP_OK ) *st = g_stream; return rc; }
 void api_set_err( const char* what ) { set_err( "%s", what ); }
 const GridView* api_cloud_view( const rs_hip_cloud* c ) { return c ? &c->view : nullptr; }
+void* api_prof_begin() { return g_prof ? (void*)prof_event() : nullptr; }
+void api_prof_end( const char* name, void* begin ) { if( begin ) prof_span( name, (hipEvent_t)begin, prof_event() ); }
 } // namespace rs

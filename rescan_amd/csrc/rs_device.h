@@ -371,5 +371,7 @@ void launch_edge_write( const EdgeLaunch& L, hipStream_t st );   // fills e1/e2/
 int             api_ready( hipStream_t* st );              // ensure_ready(); *st = the calling thread's stream
 void            api_set_err( const char* what );           // rs_hip_last_error()'s text
 const GridView* api_cloud_view( const struct ::rs_hip_cloud* c );
+void*           api_prof_begin();                          // rs_hip_profile_enable: an event on the thread's stream (null: profiling off)
+void            api_prof_end( const char* name, void* begin );   // ... and the span since then, booked under `name`
 
 } // namespace rs

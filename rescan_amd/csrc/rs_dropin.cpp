@@ -761,6 +761,39 @@ float rsd_alignment_score( const rsd_vec3_t* obj_pos, const rsd_vec3_t* obj_nor,
   return s;
 }
 
+// isect_get_overlap_factor / mgs_non_maxima_suppresion on host arrays: lvl1_* = shape->positions[1] (rasterised), lvl3_* =
+// shape->positions[3] (bounding boxes); cell 0: the clouds are only streamed, never searched
+int rsd_overlap_factor( const rsd_vec3_t* a_lvl1, int32_t a_n1, const rsd_vec3_t* a_lvl3, int32_t a_n3, const rsd_mat4_t* pose_a,
+                        const rsd_vec3_t* b_lvl1, int32_t b_n1, const rsd_vec3_t* b_lvl3, int32_t b_n3, const rsd_mat4_t* pose_b,
+                        float voxel_size, int voxelize_inside, int normalize_by_smaller, float* overlap )
+{
+  if( !a_lvl1 || !a_lvl3 || !b_lvl1 || !b_lvl3 || !pose_a || !pose_b || !overlap ) return RS_HIP_E_ARG;
+  const CloudRef a1 = cached_cloud( a_lvl1, nullptr, a_n1, 0.0f ), a3 = cached_cloud( a_lvl3, nullptr, a_n3, 0.0f );
+  const CloudRef b1 = cached_cloud( b_lvl1, nullptr, b_n1, 0.0f ), b3 = cached_cloud( b_lvl3, nullptr, b_n3, 0.0f );
+  if( !a1 || !a3 || !b1 || !b3 ) return RS_HIP_E_RUNTIME;
+  const rs_hip_isect_shape_t shapes[2] = { { a1.get(), a3.get() }, { b1.get(), b3.get() } };
+  const int32_t ia = 0, ib = 1;
+  float ov = 0.0f;
+  const int rc = rs_hip_overlap_factors( shapes, 2, &ia, (const float*)pose_a, &ib, (const float*)pose_b, 1, voxel_size, voxelize_inside,
+                                         normalize_by_smaller, &ov, nullptr );
+  if( rc ) { complain( "overlap_factor" ); return rc; }
+  *overlap = ov;
+  return rc;
+}
+
+int rsd_non_maxima_suppression( const rsd_vec3_t* lvl1, int32_t n1, const rsd_vec3_t* lvl3, int32_t n3, const rsd_vec3_t* centroid,
+                                const rsd_mat4_t* poses, const float* scores, int32_t n, float dist_threshold,
+                                int32_t* marks, int32_t* keep_idx, int32_t* n_keep )
+{
+  if( !lvl1 || !lvl3 ) return RS_HIP_E_ARG;
+  const CloudRef c1 = cached_cloud( lvl1, nullptr, n1, 0.0f ), c3 = cached_cloud( lvl3, nullptr, n3, 0.0f );
+  if( !c1 || !c3 ) return RS_HIP_E_RUNTIME;
+  const rs_hip_isect_shape_t shape = { c1.get(), c3.get() };
+  const int rc = rs_hip_nms( &shape, (const float*)centroid, (const float*)poses, scores, n, dist_threshold, marks, keep_idx, n_keep, nullptr );
+  if( rc ) complain( "non_maxima_suppression" );
+  return rc;
+}
+
 int rsd_arrangement_to_labels( const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn,
                                const rsd_vec3_t* const* obj_pos, const rsd_vec3_t* const* obj_nor, const int32_t* obj_n,
                                const rsd_mat4_t* poses, const int32_t* is_static, const int32_t* class_idx, int32_t n_plc,

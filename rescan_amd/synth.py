@@ -100,7 +100,14 @@ def make_shelf(rng, density=DENSITY, scale=1.0):
     return np.concatenate(P), np.concatenate(N)
 
 
-OBJECT_MAKERS = {"chair": make_chair, "table": make_table, "shelf": make_shelf}
+def make_crate(rng, density=DENSITY, scale=1.0):
+    """One closed box standing on the floor: the only maker whose voxelisation has INSIDE cells at 0.1 m (the others are
+    built from 4-5 cm slabs)."""
+    s = scale
+    return sample_box(rng, (0, 0.25 * s, 0), (0.6 * s, 0.5 * s, 0.7 * s), density)
+
+
+OBJECT_MAKERS = {"chair": make_chair, "table": make_table, "shelf": make_shelf, "crate": make_crate}
 # class indices in the style of an nyu40 class file (wall/floor are static, rs_database.h:257-288)
 CLASS_IDX = {"unlabelled": 0, "wall": 1, "floor": 2, "chair": 5, "table": 7, "shelf": 15}
 STATIC_CLASSES = ("wall", "floor", "unlabelled")
@@ -201,6 +208,28 @@ def perturbed_pose(pose16, rng, max_angle=0.08, max_shift=0.04):
     d = np.eye(4); d[:3, :3] = rot_y(ang); d[:3, 3] = t
     m = np.asarray(pose16, np.float64).reshape(4, 4).T @ d
     return np.ascontiguousarray(m.T.astype(np.float32).ravel())
+
+
+def nms_proposals(seed, n, span=1.0, n_previous=2, low_fraction=0.1):
+    """A pose-proposal list like the one the reference's grid search hands to its non-maximum suppression
+    (apps/pose_proposal/pose_proposal.cpp:219-240): poses on a 0.1 m lattice of the floor within +-span, rotated about +y by
+    multiples of 2 pi / 10; scores in [0, 1] rounded to two decimals (ties), a fraction of them below 0.01, and n_previous
+    off-lattice poses with score 10.0 at the end (the previous arrangement's placements, apps/pose_proposal/main.cpp:163-173).
+    Returns (poses float32 [n, 16] column-major, scores float32 [n])."""
+    rng = np.random.default_rng([seed, n])
+    steps = int(round(span / 0.1))
+    poses, scores = [], []
+    for _ in range(n - n_previous):
+        i, j = rng.integers(-steps, steps + 1, 2)
+        k = int(rng.integers(0, 10))
+        poses.append(pose_matrix(np.float32(k) * np.float32(2.0 * np.pi / 10.0), (np.float32(i) * np.float32(0.1), 0.0, np.float32(j) * np.float32(0.1))))
+        sc = np.round(rng.random() ** 2, 2)
+        scores.append(sc * 0.001 if rng.random() < low_fraction else sc)
+    for _ in range(n_previous):
+        t = rng.uniform(-span, span, 3); t[1] = 0.0
+        poses.append(pose_matrix(rng.uniform(0, 2 * np.pi), t))
+        scores.append(10.0)
+    return np.stack(poses).astype(np.float32), np.asarray(scores, np.float32)
 
 
 def write_ply(path, s):
