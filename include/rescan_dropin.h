@@ -144,6 +144,24 @@ void* rsd_coverage_create( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_ma
 float rsd_coverage_score( void* coverage, const rsd_vec3_t* const* obj_pos, const int32_t* obj_n,
                           const rsd_mat4_t* poses, const int32_t* is_static, int32_t n_plc );
 void  rsd_coverage_destroy( void* coverage );
+/* The coverage term of rsao_greedy_step's trial arrangements (arrangement_optimization.cpp:1012-1020) in one call: scores[k] =
+ * rsao__compute_scene_coverage_score of cur_arrangement + proposals[k], bit for bit (rs_hip_coverage_extensions).  base_* =
+ * cur_arrangement as for rsd_coverage_score; cand_* = the proposals' level-2 clouds and poses.  0, or an RS_HIP_E_* code with
+ * nothing written. */
+int   rsd_coverage_extensions( void* coverage, const rsd_vec3_t* const* base_pos, const int32_t* base_n, const rsd_mat4_t* base_poses,
+                               const int32_t* base_static, int32_t n_base,
+                               const rsd_vec3_t* const* cand_pos, const int32_t* cand_n, const rsd_mat4_t* cand_poses, int32_t n_cand,
+                               float* scores );
+/* rsao_compute_scene_saliency (arrangement_optimization.cpp:1109-1160, 1292-1295; apps/segment_transfer/main.cpp:337) for one
+ * scene: quality[i] replaces scn->qualities[0][i].  bbox = the scene cloud's, voxel_size = 0.15f (main.cpp:327); obj_* =
+ * rsdb->objects[o].shape level 2; proposal k = (object, rsdb->proposed_poses[scene][object][pose], rsdb_is_object_static);
+ * scene_pos / scene_class = scn->positions[0] / class_ids[0]; wall_class / floor_class = rsdb_get_class_idx (-1: absent).
+ * 0, or an RS_HIP_E_* code with nothing written. */
+int   rsd_scene_saliency( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
+                          const rsd_vec3_t* const* obj_pos, const int32_t* obj_n, int32_t n_objects,
+                          const int32_t* prop_object, const rsd_mat4_t* prop_poses, const int32_t* prop_static, int32_t n_props,
+                          const rsd_vec3_t* scene_pos, const int32_t* scene_class, int32_t n_scene,
+                          int32_t wall_class, int32_t floor_class, float* quality );
 
 /* ---- the on-disk formats either side of the path ---------------------------------
  * Pose-proposal blob (writer apps/pose_proposal/main.cpp:61-89, reader apps/segment_transfer/main.cpp:143-193):

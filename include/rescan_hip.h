@@ -419,6 +419,51 @@ int  rs_hip_coverage_scores( rs_hip_coverage_t* c, const rs_hip_cloud_t* const* 
                              const int32_t* is_static, const int32_t* first_placement, int32_t n_arrangements,
                              float* scores, int32_t* agree );
 
+/* rsao_greedy_step's trial arrangements (:1012-1020) in one call: candidate k is scored as the arrangement "base + candidate k",
+ * without a plane of the grid per candidate.  The base's placements are (base_objects[i], base_poses[16i..], base_static[i]),
+ * static ones skipped (:1095-1096); candidate k places cand_objects[k] (level-2 cloud) at cand_poses[16k..] and is always
+ * rasterised (the greedy step proposes no static object).  agree[k] (may be NULL) = base's agreeing voxels + the distinct
+ * scene-active voxels candidate k hits that the base does not; scores[k] = (float)agree[k] / (float)valid, 0 when the scene grid
+ * has no valid cell (:366-368); *base_agree (may be NULL) = the base's own count.  Every agree[k] and every bit of scores[k]
+ * equals what rs_hip_coverage_scores returns for base + candidate k, and what rsao__compute_scene_coverage_score (:344-373) does.
+ * The base is rasterised once; a candidate's bits live in the sub-box of its cells, in LDS (rs_arrange.hip). */
+int  rs_hip_coverage_extensions( rs_hip_coverage_t* c,
+                                 const rs_hip_cloud_t* const* base_objects, const float* base_poses, const int32_t* base_static, int32_t n_base,
+                                 const rs_hip_cloud_t* const* cand_objects, const float* cand_poses, int32_t n_candidates,
+                                 float* scores, int32_t* agree, int32_t* base_agree );
+/* (tests, diagnostics) Candidates whose sub-box needs at most `bytes` of LDS keep it there (default and maximum 16384); larger ones
+ * use a slab of global memory, same code, same bits.  0 sends every candidate there; bytes < 0 only reads.  Returns the previous budget. */
+int32_t rs_hip_coverage_lds_budget( int32_t bytes );
+/* (diagnostics) Candidates the process scored on the LDS route and on the slab route since the last reset. */
+void    rs_hip_coverage_extension_routes( int64_t* lds, int64_t* slab, int32_t reset );
+/* rs_hip_coverage_extensions and rs_hip_scene_saliency keep their device and pinned buffers per calling thread between calls (a bit
+ * plane of the grid, the placements, the scene points; a slab of up to 256 MB once a call took the global route).  They are not
+ * freed when the thread ends: a thread that ends while the process goes on calls this first.  Later calls allocate again. */
+int     rs_hip_arrange_release( void );
+
+/* ---- scene saliency: the per-point quality that gates the scene grid (arrangement_optimization.cpp:1109-1160) ---- */
+
+/* isect_grid3d_init (lib/rs/intersect.h:59-75) for a box, on the host: cells per axis, origin (the fattened box's minimum) and the
+ * number of cells — the size of the byte array rs_hip_scene_saliency can hand back.  RS_HIP_E_CAPACITY beyond 2e9 cells. */
+int  rs_hip_voxel_grid_shape( const float bbox_min[3], const float bbox_max[3], float voxel_size, int32_t res[3], float origin[3], int64_t* n_cells );
+
+/* rsao__compute_scene_saliency_grid (:1109-1160, called through rsao_compute_scene_saliency from apps/segment_transfer/main.cpp:337)
+ * for one scene: a grid over the scene's box (main.cpp:327 passes voxel_size 0.15f) in which ALL proposals of dynamic objects
+ * set their cells first and then ALL proposals of static objects clear theirs (:1126-1131; rsao__rasterize_proposals_to_grid,
+ * :1038-1062, level 2 of the object, msh_mat4_vec3_mul( pose, p, 1 ), cell by isect_grid3d_cell_from_world_space, intersect.h:97-109).
+ * Proposal k places objects[prop_object[k]] (its level-2 device cloud) at prop_poses[16k..]; prop_static[k] =
+ * rsdb_is_object_static of that object.  scene_pos / scene_class are the scene's LEVEL-0 positions (AoS xyz) and class ids, host
+ * arrays; wall_class / floor_class = rsdb_get_class_idx( "wall" / "floor" ), -1 where the class is absent.  quality[i] = 0.0f
+ * for a wall or floor point whatever its cell holds (:1141-1145), else 1.0f if its cell is lit and 0.0f if not or if the point
+ * lies outside the grid (:1146-1154).  grid (may be NULL; grid_capacity >= the grid's cells) receives the grid as the reference's
+ * byte array (1 = RSAO_CELL_ACTIVE).  Any number of proposals (launches of 65535 each).  Arguments are checked before a device
+ * is touched. */
+int  rs_hip_scene_saliency( const float bbox_min[3], const float bbox_max[3], float voxel_size,
+                            const rs_hip_cloud_t* const* objects, int32_t n_objects,
+                            const int32_t* prop_object, const float* prop_poses, const int32_t* prop_static, int32_t n_proposals,
+                            const float* scene_pos, const int32_t* scene_class, int64_t n_scene,
+                            int32_t wall_class, int32_t floor_class, float* quality, uint8_t* grid, int64_t grid_capacity );
+
 /* ---- voxel overlap of placed shapes, non-maximum suppression of pose proposals ---- */
 
 /* A shape is two device clouds of one object: its BOUNDARY cloud (the reference's level 1: the points that are rasterised,

@@ -90,6 +90,14 @@ SIGNATURES = {
     "rs_hip_coverage_info": (C.c_int, [C.c_void_p, i32p, f32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rs_hip_coverage_scene_grid": (C.c_int, [C.c_void_p, np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS")]),
     "rs_hip_coverage_scores": (C.c_int, [C.c_void_p, C.c_void_p, f32p, i32p, i32p, C.c_int32, f32p, C.c_void_p]),
+    "rs_hip_coverage_extensions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_coverage_lds_budget": (C.c_int32, [C.c_int32]),
+    "rs_hip_coverage_extension_routes": (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
+    "rs_hip_arrange_release": (C.c_int, []),
+    "rs_hip_voxel_grid_shape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_scene_saliency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "rs_hip_cloud_create_level": (C.c_void_p, [C.c_void_p, C.c_float, C.c_int32, C.c_float, i32p, C.POINTER(C.c_int32)]),
     "rs_hip_level_samples": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
@@ -674,6 +682,27 @@ class Coverage:
         _check(load().rs_hip_coverage_scores(self.handle, C.addressof(objs), poses, stat, first, len(arrangements), sc, ag.ctypes.data))
         return sc, ag
 
+    def extensions(self, base, candidates):
+        """rsao_greedy_step's trial arrangements in one call (rs_hip_coverage_extensions).  base: list of (Cloud, pose16, is_static)
+        — a static placement's Cloud may be None; candidates: list of (Cloud, pose16).  Returns (scores f32 [C], agree i32 [C],
+        the base's own agreeing-voxel count): candidate k scored as the arrangement base + [candidate k]."""
+        for k, p in enumerate(base):
+            if len(p) != 3 or (not p[2] and p[0] is None) or np.size(p[1]) != 16:
+                raise ValueError(f"extensions: base placement {k} is not (Cloud, pose16, is_static)")
+        for k, p in enumerate(candidates):
+            if len(p) != 2 or p[0] is None or np.size(p[1]) != 16:
+                raise ValueError(f"extensions: candidate {k} is not (Cloud, pose16)")
+        nb, nc = len(base), len(candidates)
+        bo = (C.c_void_p * max(1, nb))(*[None if p[0] is None else p[0].handle for p in base])
+        co = (C.c_void_p * max(1, nc))(*[p[0].handle for p in candidates])
+        bp = _f32(np.array([np.asarray(p[1], np.float32).ravel() for p in base], np.float32).reshape(-1, 16)) if nb else np.zeros((1, 16), np.float32)
+        cp = _f32(np.array([np.asarray(p[1], np.float32).ravel() for p in candidates], np.float32).reshape(-1, 16)) if nc else np.zeros((1, 16), np.float32)
+        bs = np.array([int(bool(p[2])) for p in base] or [0], np.int32)
+        sc, ag, ba = np.zeros(max(1, nc), np.float32), np.zeros(max(1, nc), np.int32), C.c_int32()
+        _check(load().rs_hip_coverage_extensions(self.handle, C.addressof(bo), bp.ctypes.data, bs.ctypes.data, nb, C.addressof(co), cp.ctypes.data, nc,
+                                                 sc.ctypes.data, ag.ctypes.data, C.addressof(ba)))
+        return sc[:nc], ag[:nc], ba.value
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
@@ -681,6 +710,62 @@ class Coverage:
                 self.handle = None
         except Exception:
             pass
+
+
+def coverage_lds_budget(nbytes=-1):
+    """Candidates of Coverage.extensions whose bit sub-box fits `nbytes` of LDS keep it there, larger ones use global memory (0: all of
+    them); returns the previous budget."""
+    return load().rs_hip_coverage_lds_budget(int(nbytes))
+
+
+def coverage_extension_routes(reset=False):
+    """(candidates scored on the LDS route, on the slab route) since the last reset."""
+    a, b = C.c_int64(), C.c_int64()
+    load().rs_hip_coverage_extension_routes(C.byref(a), C.byref(b), int(bool(reset)))
+    return a.value, b.value
+
+
+def arrange_release():
+    """Frees the buffers Coverage.extensions and scene_saliency keep for the calling thread (a thread that ends calls this first)."""
+    _check(load().rs_hip_arrange_release())
+
+
+def voxel_grid_shape(bbox_min, bbox_max, voxel_size):
+    """isect_grid3d_init for a box (host only): (res int32[3], origin float32[3], n_cells)."""
+    res, org, n = np.zeros(3, np.int32), np.zeros(3, np.float32), C.c_int64()
+    _check(load().rs_hip_voxel_grid_shape(_f32(bbox_min).ctypes.data, _f32(bbox_max).ctypes.data, float(np.float32(voxel_size)),
+                                          res.ctypes.data, org.ctypes.data, C.addressof(n)))
+    return res, org, n.value
+
+
+def scene_saliency(bbox_min, bbox_max, objects, prop_object, prop_poses, prop_static, scene_pos, scene_class, wall_class, floor_class,
+                   voxel_size=0.15, want_grid=False):
+    """rsao_compute_scene_saliency for one scene (rs_hip_scene_saliency).  objects: list of level-2 Clouds (None where no proposal
+    names the object); proposal k places objects[prop_object[k]] at prop_poses[k], prop_static[k] = the object is static;
+    scene_pos / scene_class: the scene's level-0 points and class ids; wall_class / floor_class: -1 where the class is absent.
+    Returns quality float32 [n] (0 or 1), and the grid as the reference's byte array if want_grid."""
+    bmin, bmax = _f32(bbox_min).ravel(), _f32(bbox_max).ravel()
+    po = np.ascontiguousarray(prop_object, np.int32).ravel()
+    pp = _f32(prop_poses).reshape(-1, 16)
+    ps = np.ascontiguousarray(prop_static, np.int32).ravel()
+    pos = _f32(scene_pos).reshape(-1, 3)
+    cls = np.ascontiguousarray(scene_class, np.int32).ravel()
+    if len(bmin) != 3 or len(bmax) != 3 or not float(voxel_size) > 0:
+        raise ValueError("scene_saliency: a box of two 3-vectors and a voxel size > 0")
+    if not (len(pp) == len(po) == len(ps)) or len(cls) != len(pos):
+        raise ValueError("scene_saliency: proposal or scene arrays of different lengths")
+    if len(po) and (po.min() < 0 or po.max() >= len(objects) or any(objects[o] is None for o in po)):
+        raise ValueError("scene_saliency: a proposal names an object outside the list or without a cloud")
+    objs = (C.c_void_p * max(1, len(objects)))(*[None if o is None else o.handle for o in objects])
+    quality = np.zeros(max(1, len(pos)), np.float32)
+    grid, cap = None, 0
+    if want_grid:
+        cap = voxel_grid_shape(bmin, bmax, voxel_size)[2]
+        grid = np.zeros(cap, np.uint8)
+    _check(load().rs_hip_scene_saliency(bmin.ctypes.data, bmax.ctypes.data, float(np.float32(voxel_size)), C.addressof(objs), len(objects),
+                                        po.ctypes.data, pp.ctypes.data, ps.ctypes.data, len(po), pos.ctypes.data, cls.ctypes.data, len(pos),
+                                        int(wall_class), int(floor_class), quality.ctypes.data, None if grid is None else grid.ctypes.data, cap))
+    return (quality[:len(pos)], grid) if want_grid else quality[:len(pos)]
 
 
 def _isect_shapes(shapes):

@@ -9,6 +9,7 @@
 #include "../../include/rescan_hip.h"
 #include "rs_device.h"
 #include "rs_math.h"
+#include "rs_voxel.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -2571,14 +2572,7 @@ extern "C" rs_hip_cloud_t* rs_hip_cloud_create_level( const rs_hip_cloud_t* base
 // scene-coverage term
 // ------------------------------------------------------------------------------------------
 
-struct rs_hip_coverage
-{
-  VoxGrid grid{};
-  float voxel_size = 0.0f, origin[3] = { 0, 0, 0 };
-  int n_words = 0;
-  long long valid = 0;
-  uint32_t* d_bits = nullptr;
-};
+// (struct rs_hip_coverage: rs_voxel.h, shared with rs_arrange.hip)
 
 extern "C" rs_hip_coverage_t* rs_hip_coverage_create( const float bbox_min[3], const float bbox_max[3], float voxel_size,
                                                       const float* scene_pos, const float* scene_quality, int64_t n_scene,
@@ -2587,20 +2581,10 @@ extern "C" rs_hip_coverage_t* rs_hip_coverage_create( const float bbox_min[3], c
   if( ensure_ready() ) return nullptr;
   if( !bbox_min || !bbox_max || !( voxel_size > 0.0f ) || n_scene < 0 || ( n_scene > 0 && !scene_pos ) ) { set_err( "coverage_create: bad arguments" ); return nullptr; }
   rs_hip_coverage_t* c = new rs_hip_coverage_t();
-  // isect_grid3d_init (lib/rs/intersect.h:59-75), same float operations
-  const float fat = 0.3f;
-  float mn[3], mx[3];
-  for( int a = 0; a < 3; ++a ) { mn[a] = bbox_min[a] - fat; mx[a] = bbox_max[a] + fat; }
-  const double cells = ( (double)std::ceil( ( mx[0] - mn[0] ) / voxel_size ) + 1 ) * ( (double)std::ceil( ( mx[1] - mn[1] ) / voxel_size ) + 1 ) *
-                       ( (double)std::ceil( ( mx[2] - mn[2] ) / voxel_size ) + 1 );
-  if( !( cells > 0 ) || cells > 2.0e9 ) { set_err( "coverage_create: %g voxels do not fit the reference's int32 cell index", cells ); delete c; return nullptr; }
-  c->grid.x_res = (int)std::ceil( ( mx[0] - mn[0] ) / voxel_size ) + 1;
-  c->grid.y_res = (int)std::ceil( ( mx[1] - mn[1] ) / voxel_size ) + 1;
-  c->grid.z_res = (int)std::ceil( ( mx[2] - mn[2] ) / voxel_size ) + 1;
-  c->grid.n_cells = c->grid.x_res * c->grid.y_res * c->grid.z_res;
-  c->grid.ox = mn[0]; c->grid.oy = mn[1]; c->grid.oz = mn[2];
-  c->grid.inv_voxel = 1.0f / voxel_size;                      // :100
-  c->voxel_size = voxel_size; for( int a = 0; a < 3; ++a ) c->origin[a] = mn[a];
+  // isect_grid3d_init (lib/rs/intersect.h:59-75), same float operations (rs_voxel.h)
+  double cells = 0.0;
+  if( !vox_grid_init( bbox_min, bbox_max, voxel_size, c->grid, &cells ) ) { set_err( "coverage_create: %g voxels do not fit the reference's int32 cell index", cells ); delete c; return nullptr; }
+  c->voxel_size = voxel_size; c->origin[0] = c->grid.ox; c->origin[1] = c->grid.oy; c->origin[2] = c->grid.oz;
   c->n_words = ( c->grid.n_cells + 31 ) / 32;
   auto fail = [&]( const char* what ) { set_err( "coverage_create: %s", what ); if( c->d_bits ) (void)hipFree( c->d_bits ); delete c; return (rs_hip_coverage_t*)nullptr; };
   if( hipMalloc( &c->d_bits, (size_t)c->n_words * 4 ) != hipSuccess ) return fail( "hipMalloc failed" );

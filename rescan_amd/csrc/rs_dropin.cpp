@@ -897,6 +897,63 @@ float rsd_coverage_score( void* coverage, const rsd_vec3_t* const* obj_pos, cons
 
 void rsd_coverage_destroy( void* coverage ) { rs_hip_coverage_destroy( (rs_hip_coverage_t*)coverage ); }
 
+int rsd_coverage_extensions( void* coverage, const rsd_vec3_t* const* base_pos, const int32_t* base_n, const rsd_mat4_t* base_poses,
+                             const int32_t* base_static, int32_t n_base,
+                             const rsd_vec3_t* const* cand_pos, const int32_t* cand_n, const rsd_mat4_t* cand_poses, int32_t n_cand,
+                             float* scores )
+{
+  if( !coverage || n_base < 0 || n_cand < 0 || ( n_base > 0 && ( !base_pos || !base_n || !base_poses || !base_static ) ) ||
+      ( n_cand > 0 && ( !cand_pos || !cand_n || !cand_poses || !scores ) ) ) return RS_HIP_E_ARG;
+  for( int i = 0; i < n_base; ++i ) if( !base_static[i] && ( !base_pos[i] || base_n[i] < 0 ) ) return RS_HIP_E_ARG;
+  for( int i = 0; i < n_cand; ++i ) if( !cand_pos[i] || cand_n[i] < 0 ) return RS_HIP_E_ARG;
+  // every cloud is HELD for the call (see rsd_arrangement_to_labels)
+  std::vector<CloudRef> held( (size_t)n_base + (size_t)n_cand );
+  std::vector<const rs_hip_cloud_t*> objs( held.size() );
+  for( int i = 0; i < n_base + n_cand; ++i )
+  {
+    const bool base = i < n_base;
+    if( base && base_static[i] ) continue;
+    const rsd_vec3_t* pos = base ? base_pos[i] : cand_pos[i - n_base];
+    held[i] = cached_cloud( pos, nullptr, base ? base_n[i] : cand_n[i - n_base], -1.0f );
+    if( !held[i] ) return RS_HIP_E_RUNTIME;
+    objs[i] = held[i].get();
+  }
+  const int rc = rs_hip_coverage_extensions( (rs_hip_coverage_t*)coverage, objs.data(), (const float*)base_poses, base_static, n_base,
+                                             objs.data() + n_base, (const float*)cand_poses, n_cand, scores, nullptr, nullptr );
+  if( rc ) complain( "coverage_extensions" );
+  return rc;
+}
+
+int rsd_scene_saliency( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
+                        const rsd_vec3_t* const* obj_pos, const int32_t* obj_n, int32_t n_objects,
+                        const int32_t* prop_object, const rsd_mat4_t* prop_poses, const int32_t* prop_static, int32_t n_props,
+                        const rsd_vec3_t* scene_pos, const int32_t* scene_class, int32_t n_scene,
+                        int32_t wall_class, int32_t floor_class, float* quality )
+{
+  // everything rs_hip_scene_saliency would refuse, before a cloud is uploaded
+  if( !bbox_min || !bbox_max || !( voxel_size > 0.0f ) || n_objects < 0 || n_props < 0 || n_scene < 0 ||
+      ( n_props > 0 && ( !obj_pos || !obj_n || !prop_object || !prop_poses || !prop_static ) ) ||
+      ( n_scene > 0 && ( !scene_pos || !scene_class || !quality ) ) ) return RS_HIP_E_ARG;
+  for( int32_t k = 0; k < n_props; ++k )
+    if( prop_object[k] < 0 || prop_object[k] >= n_objects || !obj_pos[prop_object[k]] || obj_n[prop_object[k]] < 0 ) return RS_HIP_E_ARG;
+  // only the objects that some proposal names are uploaded; all of them are HELD for the call
+  std::vector<CloudRef> held( (size_t)n_objects );
+  std::vector<const rs_hip_cloud_t*> objs( held.size(), nullptr );
+  for( int32_t k = 0; k < n_props; ++k )
+  {
+    const int32_t o = prop_object[k];
+    if( held[o] ) continue;
+    held[o] = cached_cloud( obj_pos[o], nullptr, obj_n[o], -1.0f );
+    if( !held[o] ) return RS_HIP_E_RUNTIME;
+    objs[o] = held[o].get();
+  }
+  const int rc = rs_hip_scene_saliency( (const float*)bbox_min, (const float*)bbox_max, voxel_size, objs.data(), n_objects,
+                                        prop_object, (const float*)prop_poses, prop_static, n_props,
+                                        (const float*)scene_pos, scene_class, n_scene, wall_class, floor_class, quality, nullptr, 0 );
+  if( rc ) complain( "scene_saliency" );
+  return rc;
+}
+
 // ---- on-disk formats -------------------------------------------------------------------------
 
 int rsd_pose_bin_write( const char* path, int32_t n_arrays, const int32_t* counts, const float* records )

@@ -1,5 +1,6 @@
 // librescan_hip device code (gfx950, wave64) — label transfer, full rows, level builder, neighbourhood edges, coverage voxels
 #include "rs_search.h"
+#include "rs_voxel.h"
 
 namespace rs {
 
@@ -731,14 +732,7 @@ void launch_edge_write( const EdgeLaunch& L, hipStream_t st )
 // once and the others race on atomicOr — the first to set a bit counts it.
 // ------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ int voxel_of( const VoxGrid& g, float x, float y, float z )
-{
-  const int cx = (int)floorf( ( x - g.ox ) * g.inv_voxel );     // intersect.h:101-103
-  const int cy = (int)floorf( ( y - g.oy ) * g.inv_voxel );
-  const int cz = (int)floorf( ( z - g.oz ) * g.inv_voxel );
-  if( cx < 0 || cx >= g.x_res || cy < 0 || cy >= g.y_res || cz < 0 || cz >= g.z_res ) return -1;
-  return cy * g.x_res * g.z_res + cz * g.x_res + cx;            // :108
-}
+// (voxel_of: rs_voxel.h, shared with rs_arrange.hip)
 
 __global__ __launch_bounds__( BLOCK ) void k_voxel_mark( VoxGrid g, const float* pos, const float* quality, float threshold, long long n, uint32_t* bits )
 {
