@@ -399,7 +399,9 @@ int rs_hip_compute_neighborhood( const rs_hip_cloud_t* cloud, int32_t max_nn, fl
 /* The voxel grid of lib/rs/intersect.h:59-109 over a scene's bounding box (isect_grid3d_init: fattened by
  * 0.3, ceilf(extent/voxel)+1 cells per axis) with the scene's level-2 points rasterised into it
  * (rsao_rasterize_scene_to_grid, apps/segment_transfer/arrangement_optimization.cpp:1064-1079: points
- * with quality < threshold are skipped; quality may be NULL).  One bit per voxel on the device. */
+ * with quality < threshold are skipped; quality may be NULL).  One bit per voxel on the device.
+ * In rs_hip_coverage_create, _scores and _extensions a point with a NaN or infinite coordinate (after its pose) lies outside the
+ * grid, like any point whose floored cell coordinate is not in [0, res): it sets, clears and reads no cell. */
 typedef struct rs_hip_coverage rs_hip_coverage_t;
 rs_hip_coverage_t* rs_hip_coverage_create( const float bbox_min[3], const float bbox_max[3], float voxel_size,
                                            const float* scene_pos, const float* scene_quality, int64_t n_scene,
@@ -457,7 +459,8 @@ int  rs_hip_voxel_grid_shape( const float bbox_min[3], const float bbox_max[3], 
  * for a wall or floor point whatever its cell holds (:1141-1145), else 1.0f if its cell is lit and 0.0f if not or if the point
  * lies outside the grid (:1146-1154).  grid (may be NULL; grid_capacity >= the grid's cells) receives the grid as the reference's
  * byte array (1 = RSAO_CELL_ACTIVE).  Any number of proposals (launches of 65535 each).  Arguments are checked before a device
- * is touched. */
+ * is touched.  A point with a NaN or infinite coordinate (after its pose) lies outside the grid, like any point whose floored cell
+ * coordinate is not in [0, res): it sets, clears and reads no cell. */
 int  rs_hip_scene_saliency( const float bbox_min[3], const float bbox_max[3], float voxel_size,
                             const rs_hip_cloud_t* const* objects, int32_t n_objects,
                             const int32_t* prop_object, const float* prop_poses, const int32_t* prop_static, int32_t n_proposals,

@@ -39,14 +39,18 @@ inline bool vox_grid_init( const float bbox_min[3], const float bbox_max[3], flo
 }
 
 #ifdef __HIPCC__
-// isect_grid3d_cell_from_world_space (:97-109): the cell's index in the reference's byte array, -1 outside the grid
+// isect_grid3d_cell_from_world_space (:97-109): the cell's index in the reference's byte array, -1 outside the grid.  The range
+// test is made on the floored floats BEFORE the conversion: a NaN, an infinity or a value no int32 holds fails it, as the
+// reference's conversion to INT_MIN does on its x86 build (a device conversion would make cell 0 of a NaN).  Every finite input
+// keeps its cell while the resolutions are below 2^24, where (float)res is exact, as in isect_rasterise (rs_isect.hip); past
+// 2^24 cells along one axis fp32 coordinates no longer tell neighbouring cells apart.
 __device__ __forceinline__ int voxel_of( const VoxGrid& g, float x, float y, float z )
 {
-  const int cx = (int)floorf( ( x - g.ox ) * g.inv_voxel );     // intersect.h:101-103
-  const int cy = (int)floorf( ( y - g.oy ) * g.inv_voxel );
-  const int cz = (int)floorf( ( z - g.oz ) * g.inv_voxel );
-  if( cx < 0 || cx >= g.x_res || cy < 0 || cy >= g.y_res || cz < 0 || cz >= g.z_res ) return -1;
-  return cy * g.x_res * g.z_res + cz * g.x_res + cx;            // :108
+  const float fx = floorf( ( x - g.ox ) * g.inv_voxel );        // intersect.h:101-103
+  const float fy = floorf( ( y - g.oy ) * g.inv_voxel );
+  const float fz = floorf( ( z - g.oz ) * g.inv_voxel );
+  if( !( fx >= 0.0f && fx < (float)g.x_res && fy >= 0.0f && fy < (float)g.y_res && fz >= 0.0f && fz < (float)g.z_res ) ) return -1;
+  return (int)fy * g.x_res * g.z_res + (int)fz * g.x_res + (int)fx;      // :108
 }
 #endif
 

@@ -20,13 +20,18 @@ def xform(pose, pts):
     """msh_mat4_vec3_mul( pose, p, 1 ): column-major, products summed left to right in fp32."""
     m = np.asarray(pose, F).ravel()
     pts = np.asarray(pts, F).reshape(-1, 3)
-    return np.stack([m[r] * pts[:, 0] + m[4 + r] * pts[:, 1] + m[8 + r] * pts[:, 2] + F(1.0) * m[12 + r] for r in range(3)], axis=1)
+    with np.errstate(invalid="ignore"):                     # (0 * inf of a non-finite point: NaN, as in the reference)
+        return np.stack([m[r] * pts[:, 0] + m[4 + r] * pts[:, 1] + m[8 + r] * pts[:, 2] + F(1.0) * m[12 + r] for r in range(3)], axis=1)
 
 
 def cell_coords(origin, voxel, pts):
-    """floorf( ( p - origin ) * ( 1.0f / voxel ) ) per axis (intersect.h:100-103), as integers."""
+    """floorf( ( p - origin ) * ( 1.0f / voxel ) ) per axis (intersect.h:100-103), as integers.  A floor that no int32 holds (NaN,
+    +-inf, beyond 2^31) becomes INT_MIN, as the reference's x86 conversion makes it: outside every grid."""
     inv = F(1.0) / F(voxel)
-    return np.floor((np.asarray(pts, F).reshape(-1, 3) - origin[None, :]) * inv).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        f = np.floor((np.asarray(pts, F).reshape(-1, 3) - origin[None, :]) * inv)
+        fits = np.abs(f) < F(2147483648.0)                     # (False for NaN)
+    return np.where(fits, f, F(-2147483648.0)).astype(np.int64)
 
 
 def cells(origin, res, voxel, pts):

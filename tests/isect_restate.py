@@ -44,7 +44,10 @@ def grid_of(box_a, box_b, voxel):
 
 def cells(pose16, boundary, origin, voxel):
     o = xform(pose16, boundary) - origin[None, :]
-    return np.floor(o / F(voxel)).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        f = np.floor(o / F(voxel))
+        fits = np.abs(f) < F(2147483648.0)                 # (False for NaN: no cell of any grid, like a floor beyond int32)
+    return np.where(fits, f, F(-1.0)).astype(np.int64)
 
 
 def boundary_grid(pose16, boundary, origin, res, voxel):
@@ -56,7 +59,9 @@ def boundary_grid(pose16, boundary, origin, res, voxel):
     return g
 
 
-def _inside_along(b, axis):
+def parities(b, axis):
+    """(forward, backward): per cell, whether an odd number of "FREE directly after BOUNDARY" transitions lies at or before it,
+    counted from the low end and from the high end of its line along `axis` (intersect.h:126-161)."""
     prev = np.roll(b, 1, axis=axis)
     idx = [slice(None)] * 3
     idx[axis] = 0
@@ -67,6 +72,11 @@ def _inside_along(b, axis):
     fwd = np.cumsum(~b & prev, axis=axis) % 2 == 1
     tb = ~b & nxt
     bwd = np.flip(np.cumsum(np.flip(tb, axis), axis=axis), axis) % 2 == 1
+    return fwd, bwd
+
+
+def _inside_along(b, axis):
+    fwd, bwd = parities(b, axis)
     return ~b & fwd & bwd
 
 
@@ -92,8 +102,9 @@ def overlap(shape_a, pose_a, shape_b, pose_b, voxel, inside, by_smaller):
     return (F(both) / F(denom) if denom > 0 else F(1.0)), (ca, cb, both)
 
 
-def nms(shape, centroid, poses, scores, dist_threshold):
-    """marks (1 keep, 2 discard), keep_idx, rounds, and the discards that overlap alone decided."""
+def nms(shape, centroid, poses, scores, dist_threshold, trace=None):
+    """marks (1 keep, 2 discard), keep_idx, rounds, and the discards that overlap alone decided.  `trace` (a list) receives
+    (round, i, grid resolution or None) for every pair the cheap tests leave to the overlap."""
     n = len(scores)
     scores = np.asarray(scores, F)
     if n and not np.all(scores > F(-1e9)):
@@ -114,6 +125,9 @@ def nms(shape, centroid, poses, scores, dist_threshold):
             if dist < F(dist_threshold) or scores[i] < F(0.01):
                 marks[i] = 2
                 continue
+            if trace is not None:
+                ba, bb = box(poses[best], shape[1]), box(poses[i], shape[1])
+                trace.append((rounds, int(i), grid_of(ba, bb, F(0.1))[1] if boxes_intersect(ba, bb) else None))
             ov, _ = overlap(shape, poses[best], shape, poses[i], F(0.1), 1, 0)
             if ov > F(0.5):
                 marks[i] = 2

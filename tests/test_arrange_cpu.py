@@ -134,6 +134,103 @@ def test_restatement_reproduces_every_count_and_score_bit(name):
     assert n_cand > 150
 
 
+def hard_fixture():
+    return load_golden("arrange_hard.npz")
+
+
+def test_hard_fixture_is_small_and_holds_every_case():
+    """tests/golden/arrange_hard.npz (tools/arrange_fixture/gen.py --hard): EVERY hostile case of tests/hard_shapes.py went through
+    the reference unchanged, each cloud as an object's level 2 or as the scene — the candidate of no points and the clouds with NaN
+    and infinite coordinates included — so none is pinned by the restatement alone.  Only the predicted ROUTE of a candidate (its
+    live sub-box's bytes) has no counterpart in the reference.  The file holds lengths and CRCs instead of clouds."""
+    import hard_shapes as H
+    g = hard_fixture()
+    biggest = max(os.path.getsize(os.path.join(ROOT, "tests", "golden", f)) for f in os.listdir(os.path.join(ROOT, "tests", "golden"))
+                  if f.endswith(".npz") and not f.startswith("arrange_"))
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "arrange_hard.npz")) <= biggest
+    for voxel, cell0 in H.ARR_CASES:
+        a, s = H.arrangement(voxel, cell0), H.saliency_case(voxel, cell0)
+        pre = H.arr_key("cov", voxel, cell0)
+        assert (g[pre + "crc"] == H.cloud_crcs(a["scene"], a["objects"])).all()          # the regenerated clouds are the ones the reference saw
+        assert [n.decode() for n in g[pre + "names"]] == a["names"] and len(g[pre + "agree"]) == len(a["cands"]) == len(g[pre + "score"])
+        assert (g[H.arr_key("sal", voxel, cell0) + "crc"] == H.cloud_crcs(s["scene"], s["objects"])).all()
+
+
+@pytest.mark.parametrize("voxel,cell0", [(0.05, True), (0.05, False), (0.15, True), (0.15, False)])
+def test_restatement_reproduces_the_hard_fixture(voxel, cell0):
+    """The reference's own scene grid, counts, score bits, saliency grid and qualities of the hostile cases, IDENTICALLY — among them
+    what the reference makes of a NaN or infinite coordinate: outside the grid, so cell 0 is active / lit only where a finite point is."""
+    import hard_shapes as H
+    g = hard_fixture()
+    a, grid, base_agree, fresh, agree, scores, _ = H.arrangement_expectations(voxel, cell0)
+    pre = H.arr_key("cov", voxel, cell0)
+    want = np.unpackbits(g[pre + "grid"])[:len(grid)]
+    assert (g[pre + "res"] == a["res"]).all() and want[0] == int(cell0) and int(want.sum()) == int(g[pre + "valid"])
+    assert grid.tobytes() == want.tobytes()
+    assert base_agree == int(g[pre + "base_agree"]) and (agree == g[pre + "agree"]).all() and scores.tobytes() == g[pre + "score"].tobytes()
+    assert R.coverage(grid, H.ARR_BMIN, H.ARR_BMAX, voxel, a["objects"], a["base"])[2].view(np.uint32) == g[pre + "base_score"].view(np.uint32)
+    s = H.saliency_case(voxel, cell0)
+    sal, quality = R.saliency(H.ARR_BMIN, H.ARR_BMAX, voxel, s["objects"], s["prop_obj"], s["prop_pose"], s["prop_static"], s["scene"], s["cls"], -1, 2)
+    pre = H.arr_key("sal", voxel, cell0)
+    want = np.unpackbits(g[pre + "grid"])[:len(sal)]
+    assert want[0] == int(cell0) and sal.tobytes() == want.tobytes() and quality.tobytes() == g[pre + "quality"].tobytes()
+
+
+@pytest.mark.parametrize("voxel,cell0", [(0.05, True), (0.05, False), (0.15, True), (0.15, False)])
+def test_hard_candidates_hold_every_case(voxel, cell0):
+    import hard_shapes as H
+    a, grid, base_agree, fresh, agree, scores, need = H.arrangement_expectations(voxel, cell0)
+    origin, res = R.grid_shape(H.ARR_BMIN, H.ARR_BMAX, voxel)
+    assert (res == a["res"]).all() and base_agree > 0
+    # the scene holds NaN and infinite points; cell 0 is active only by the finite point of the cell0 run.  Per the restatement a
+    # non-finite scene point is outside: one taken for cell 0 would light it in the run without that point
+    assert not np.isfinite(a["scene"]).all() and np.isnan(a["scene"]).all(1).any() and grid[0] == int(cell0)
+    assert int(grid.sum()) == int(H.arrangement_expectations(voxel, True)[1].sum()) - int(not cell0)
+    f = dict(zip(a["names"], fresh))
+    b = dict(zip(a["names"], need))
+    n_pts = {name: len(a["objects"][o]) for name, (o, _) in zip(a["names"], a["cands"])}
+    for k in (1, 255, 256, 257, 5000):
+        assert n_pts[f"three_cells_{k}"] == k and f[f"three_cells_{k}"] == min(k, 3) and f[f"spread_cells_{k}"] == min(k, 3)      # cells, not points
+        assert b[f"three_cells_{k}"] == 4 and (k < 3 or b[f"spread_cells_{k}"] > 64 * 4)                  # ... in one word, and over several waves' words
+    assert f["off_grid"] == f["inside_base"] == f["scene_inactive"] == f["empty"] == f["non_finite"] == 0
+    assert b["off_grid"] == b["inside_base"] == b["scene_inactive"] == b["empty"] == b["non_finite"] == 0        # no sub-box is made
+    assert n_pts["inside_base"] > 0 and n_pts["scene_inactive"] > 0 and n_pts["empty"] == 0
+    rod = a["objects"][a["cands"][a["names"].index("rod")][0]]
+    cc = R.cell_coords(origin, voxel, rod)
+    ext = cc.max(0) - cc.min(0) + 1
+    assert f["rod"] == len(rod) and (ext == len(rod)).all() and len(rod) >= 10 and b["rod"] == (len(rod) ** 3 + 31) // 32 * 4 and b["rod"] <= 16384
+    assert len({int(v) >> 5 for v in (cc - cc.min(0)) @ np.array([1, len(rod) ** 2, len(rod)])}) >= 10       # the bit index crosses many words
+    assert f["plate_yz"] == n_pts["plate_yz"] == 5 * (int(res[2]) - 6) and int(res[2]) - 6 > 5         # 5 cells along y, more along z
+    for axis, name in enumerate(("faces_x", "faces_y", "faces_z")):
+        pts = a["objects"][a["cands"][a["names"].index(name)][0]]
+        c = R.cell_coords(origin, voxel, pts)[:, axis]
+        t = (pts[:, axis] - origin[axis]) * (F(1.0) / F(voxel))
+        assert (c == -1).any() and (c == 0).any() and (c == res[axis] - 1).any() and (c == res[axis]).any()      # one step outside on either side
+        assert (t == 0).any() and (t == F(res[axis])).any() and (t == np.floor(t)).sum() >= 3 and f[name] > 0    # floorf of exactly 0 and of exactly res
+
+
+@pytest.mark.parametrize("voxel", (0.05, 0.15))
+def test_hard_saliency_holds_every_case(voxel):
+    import hard_shapes as H
+    for cell0 in (False, True):
+        s = H.saliency_case(voxel, cell0)
+        grid, quality = R.saliency(H.ARR_BMIN, H.ARR_BMAX, voxel, s["objects"], s["prop_obj"], s["prop_pose"], s["prop_static"], s["scene"], s["cls"], -1, 2)
+        origin, res = R.grid_shape(H.ARR_BMIN, H.ARR_BMAX, voxel)
+        dyn = R.cells(origin, res, voxel, s["objects"][0]); sta = R.cells(origin, res, voxel, s["objects"][1])
+        assert s["prop_static"][0] == 1 and s["prop_static"][1] == 0                   # the static proposal is listed first ...
+        both = np.intersect1d(dyn, sta)
+        assert len(both) > 0 and (grid[both] == 0).all() and grid[np.setdiff1d(dyn, sta)].all()       # ... and still clears what the dynamic one lit
+        c0 = R.cells(origin, res, voxel, s["scene"])
+        lit = (c0 >= 0) & (grid[np.maximum(c0, 0)] == 1)
+        assert (lit & (s["cls"] == 2)).any() and (quality[lit & (s["cls"] == 2)] == 0).all()      # floor points in lit cells
+        assert (lit & (s["cls"] == -1)).any() and (quality[lit & (s["cls"] == -1)] == 0).all()    # class -1 with wall_idx -1: "wall", quality 0
+        assert (quality[lit & (s["cls"] == 1)] == 1).all() and (lit & (s["cls"] == 1)).any()
+        # non-finite coordinates light and read nothing: cell 0 is lit only by the finite point of the second run
+        wild = R.cells(origin, res, voxel, s["objects"][2])
+        assert (wild[:6] == -1).all() and grid[0] == int(cell0) and (wild == 0).sum() == int(cell0)
+        assert (c0[-4:-1] == -1).all() and (quality[-4:-1] == 0).all() and c0[-1] == 0 and quality[-1] == F(cell0)
+
+
 def test_new_symbols_exist(built):
     out = subprocess.check_output(["nm", "-D", "--defined-only", LIB], text=True)
     for s in ("rs_hip_scene_saliency", "rs_hip_coverage_extensions", "rs_hip_coverage_lds_budget", "rs_hip_coverage_extension_routes", "rs_hip_voxel_grid_shape",

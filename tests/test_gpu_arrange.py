@@ -1,7 +1,8 @@
 """GPU: rs_hip_scene_saliency and rs_hip_coverage_extensions against the reference's own numbers (tests/golden/arrange_*.npz,
 tools/arrange_fixture), byte for byte and bit for bit: saliency grid and qualities; every candidate's count and score bits, also
 against rs_hip_coverage_scores on base + candidate computed here; the LDS route and the global-slab route; two consecutive calls;
-and the same through the shim's rsd_scene_saliency / rsd_coverage_extensions.  No tolerances: every compared quantity is an integer,
+and the same through the shim's rsd_scene_saliency / rsd_coverage_extensions; the hostile cases of tests/hard_shapes.py against
+arrange_hard.npz.  No tolerances: every compared quantity is an integer,
 a 0 / 1 float or a float whose bits the reference fixes."""
 import ctypes as C
 import os
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
-from test_arrange_cpu import NAMES, fixture, trials
+from test_arrange_cpu import NAMES, fixture, hard_fixture, trials
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -154,3 +155,73 @@ def test_the_shim_gives_the_same(capi, cases, name):
                      C.addressof(cptr), cn.ctypes.data, cp.ctypes.data if len(cand) else None, len(cand), sc.ctypes.data)
             assert rc == 0 and (bits(sc[:len(cand)]) == bits(g[pre + "score"])).all(), (j, t)
         lib.rsd_coverage_destroy(h)
+
+
+HARD = [(0.05, True), (0.05, False), (0.15, True), (0.15, False)]
+
+
+@pytest.fixture(scope="module")
+def hard():
+    return hard_fixture()
+
+
+@pytest.mark.parametrize("voxel,cell0", HARD)
+def test_hard_candidates_are_the_references(capi, hard, voxel, cell0):
+    """The hostile candidates of tests/hard_shapes.py (thousands of points in three cells, off the grid, inside the base, on inactive
+    cells, empty, NaN and infinite coordinates, a diagonal rod whose sub-box fits the LDS budget exactly, points on cell faces and on
+    the grid's outer faces) against the reference's own numbers (tests/golden/arrange_hard.npz): the scene grid — whose cloud holds
+    NaN and infinite points, with cell 0 active only in the run that has a finite point there —, every count and every score bit.
+    The route of every candidate is predicted from its live sub-box (tests/ao_restate.py; the reference has no sub-boxes) and
+    checked against the route counters."""
+    import hard_shapes as H
+    a, _, _, _, _, _, need = H.arrangement_expectations(voxel, cell0)
+    pre = H.arr_key("cov", voxel, cell0)
+    assert (hard[pre + "crc"] == H.cloud_crcs(a["scene"], a["objects"])).all()
+    want_grid = np.unpackbits(hard[pre + "grid"])[:int(a["res"].prod())]
+    base_agree, agree, scores = int(hard[pre + "base_agree"]), hard[pre + "agree"], hard[pre + "score"]
+    clouds = [capi.Cloud(p, None, 0.0) for p in a["objects"]]
+    cov = capi.Coverage(H.ARR_BMIN, H.ARR_BMAX, a["scene"], None, voxel, 0.0)
+    grid = cov.scene_grid()
+    assert grid[0] == int(cell0) == want_grid[0] and cov.valid_cells == int(hard[pre + "valid"])      # a non-finite scene point lights nothing
+    assert grid.tobytes() == want_grid.tobytes()
+    b = [(clouds[o], p, s) for o, p, s in a["base"]]
+    c = [(clouds[o], p) for o, p in a["cands"]]
+    rod = need[a["names"].index("rod")]
+    default = capi.coverage_lds_budget(-1)
+    try:
+        for budget in (default, rod, rod - 4, 0) if cell0 else (default, 0):
+            capi.coverage_lds_budget(budget)
+            capi.coverage_extension_routes(reset=True)
+            sc, ag, ba = cov.extensions(b, c)
+            assert ba == base_agree and (ag == agree).all(), (budget, [(n, int(x), int(y)) for n, x, y in zip(a["names"], ag, agree) if x != y])
+            assert (bits(sc) == bits(scores)).all()
+            assert capi.coverage_extension_routes() == (sum(v <= budget for v in need), sum(v > budget for v in need)), budget
+            sc2, ag2, ba2 = cov.extensions(b, c)
+            assert (ag2 == ag).all() and (bits(sc2) == bits(sc)).all() and ba2 == ba
+        assert rod <= default and sum(v > rod for v in need) < sum(v > rod - 4 for v in need)             # exactly the budget: LDS; 4 bytes less: the slab
+        # the same numbers from whole arrangements
+        capi.coverage_lds_budget(default)
+        sc_full, ag_full = cov.scores([b + [(cl, p, 0)] for cl, p in c])
+        assert (ag_full == agree).all() and (bits(sc_full) == bits(scores)).all()
+        sc_b, ag_b = cov.scores([b])
+        assert ag_b[0] == base_agree and bits(sc_b)[0] == bits(hard[pre + "base_score"])[0]
+    finally:
+        capi.coverage_lds_budget(default)
+
+
+@pytest.mark.parametrize("voxel,cell0", HARD)
+def test_hard_saliency_is_the_references(capi, hard, voxel, cell0):
+    """Phase order against list order, wall and floor points in lit cells, class -1 with wall_idx -1, and non-finite coordinates: a
+    NaN, +inf or -inf coordinate lights, clears and reads no cell — cell 0 least of all (a device float-to-int conversion of NaN is
+    0) — as the reference recorded it in tests/golden/arrange_hard.npz."""
+    import hard_shapes as H
+    s = H.saliency_case(voxel, cell0)
+    pre = H.arr_key("sal", voxel, cell0)
+    assert (hard[pre + "crc"] == H.cloud_crcs(s["scene"], s["objects"])).all()
+    clouds = [capi.Cloud(p, None, 0.0) for p in s["objects"]]
+    q, grid = capi.scene_saliency(H.ARR_BMIN, H.ARR_BMAX, clouds, s["prop_obj"], s["prop_pose"], s["prop_static"], s["scene"], s["cls"], -1, 2,
+                                  voxel_size=voxel, want_grid=True)
+    want_grid = np.unpackbits(hard[pre + "grid"])[:len(grid)]
+    assert grid[0] == int(cell0) == want_grid[0], (cell0, grid[0])
+    assert grid.tobytes() == want_grid.tobytes() and q.tobytes() == hard[pre + "quality"].tobytes()
+    assert q[-1] == F(cell0) and (q[-4:-1] == 0).all()

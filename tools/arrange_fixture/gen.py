@@ -15,7 +15,16 @@ Per fixture: a room scan of a few thousand level-0 points (level 2 = every third
 table, a static wall, a wall-sized dynamic partition, clouds of 1 / 63 / 64 / 65 / 300 points, a lattice cloud), pose proposals on
 the voxel lattice, the saliency at voxel 0.15 and 0.05, and coverage sets (voxel, threshold) = (0.05, 0.5), (0.15, 0.5), (0.05, 2.0:
 no valid cell) with three trials each: empty base, base with a static placement, zero candidates.  child() asserts every case the
-tests rely on."""
+tests rely on.
+
+    python tools/arrange_fixture/gen.py --hard
+
+writes tests/golden/arrange_hard.npz instead: the hostile candidates and saliency cases of tests/hard_shapes.py (arrangement and
+saliency_case, at voxel 0.05 and 0.15, with and without a finite point in cell 0) through the same three reference functions, every
+cloud handed over unchanged as an object's level 2 or as the scene.  The file holds each cloud's length and CRC, not the cloud (the
+tests regenerate them), the scene grids, the saliency grids and qualities, and per candidate the count and score bits of base +
+candidate.  Every case runs: the candidate of no points and the clouds with NaN and infinite coordinates included.  What the
+reference does not have is the sub-box of a candidate, so the routes the tests predict are the restatement's alone."""
 import argparse
 import ctypes as C
 import os
@@ -257,6 +266,57 @@ def child(lib, out_dir, name):
     sys.stdout.flush()
 
 
+def hard_child(lib, out_dir):
+    """arrange_hard.npz.  One class table ("nowall": no wall class, "unlabelled" is static) and one database per case."""
+    import hard_shapes as H
+    out = {}
+    for voxel, cell0 in H.ARR_CASES:
+        # ---- coverage: base + every candidate ----
+        a = H.arrangement(voxel, cell0)
+        ref = Ref(lib, FIXTURES["nowall"])
+        for k, pos in enumerate(a["objects"]):
+            assert ref.add_object(pos, 5, k) == k and not ref.L.fx_is_static(ref.h, k)
+        scene = np.ascontiguousarray(a["scene"], F)
+        cls, q = np.zeros(len(scene), np.int32), np.ones(len(scene), F)
+        ref.L.fx_set_scene(ref.h, fp(scene), fp(cls), fp(q), len(scene), fp(scene), fp(q), len(scene), fp(H.ARR_BMIN), fp(H.ARR_BMAX))
+        res, grid = ref.scene_grid(voxel, 0.0)
+        assert (res == a["res"]).all() and grid[0] == int(cell0)
+        bo = np.array([o for o, _, _ in a["base"]], np.int32); bp = np.array([p for _, p, _ in a["base"]], F).reshape(-1, 16)
+        assert not any(s for _, _, s in a["base"])
+        bscore, bagree = ref.coverage(bo, bp)
+        agree, score = np.zeros(len(a["cands"]), np.int32), np.zeros(len(a["cands"]), F)
+        for k, (o, p) in enumerate(a["cands"]):
+            score[k], agree[k] = ref.coverage(np.append(bo, o), np.concatenate([bp, np.asarray(p, F).reshape(1, 16)]))
+        pre = H.arr_key("cov", voxel, cell0)
+        out[pre + "crc"], out[pre + "names"], out[pre + "res"] = H.cloud_crcs(scene, a["objects"]), np.array(a["names"], "S24"), res
+        out[pre + "grid"], out[pre + "valid"] = np.packbits(grid), np.int32((grid > 0).sum())
+        out[pre + "base_agree"], out[pre + "base_score"], out[pre + "agree"], out[pre + "score"] = np.int32(bagree), bscore, agree, score
+        f = dict(zip(a["names"], agree - bagree))
+        assert set(np.unique(grid)) == {0, 1} and f["non_finite"] == f["off_grid"] == f["empty"] == 0 and f["three_cells_5000"] == 3, f
+        print(f"hard: coverage voxel {voxel} cell0 {int(cell0)}: {int((grid > 0).sum())} valid cells, base agree {bagree}, fresh {dict((k, int(v)) for k, v in f.items())}")
+        # ---- saliency ----
+        s = H.saliency_case(voxel, cell0)
+        ref = Ref(lib, FIXTURES["nowall"])
+        assert ref.class_idx("wall") == -1 and ref.class_idx("floor") == 2
+        static = {int(o): int(st) for o, st in zip(s["prop_obj"], s["prop_static"])}
+        for k, pos in enumerate(s["objects"]):
+            assert ref.add_object(pos, 0 if static.get(k, 1) else 5, k) == k and ref.L.fx_is_static(ref.h, k) == static.get(k, 1)
+        scene, cls = np.ascontiguousarray(s["scene"], F), np.ascontiguousarray(s["cls"], np.int32)
+        q = np.full(len(scene), 0.25, F)
+        ref.L.fx_set_scene(ref.h, fp(scene), fp(cls), fp(q), len(scene), fp(scene), fp(q), len(scene), fp(H.ARR_BMIN), fp(H.ARR_BMAX))
+        for o, p in zip(s["prop_obj"], s["prop_pose"]):
+            ref.L.fx_add_proposal(ref.h, int(o), fp(np.ascontiguousarray(p, F)))
+        res, org, grid = ref.saliency(voxel)
+        pre = H.arr_key("sal", voxel, cell0)
+        out[pre + "crc"], out[pre + "res"], out[pre + "grid"], out[pre + "quality"] = H.cloud_crcs(scene, s["objects"]), res, np.packbits(grid), q.copy()
+        assert set(np.unique(q)) == {F(0.0), F(1.0)} and grid[0] == int(cell0) and q[-1] == F(cell0), (grid[0], q[-4:])
+        print(f"hard: saliency voxel {voxel} cell0 {int(cell0)}: {int(grid.sum())} lit cells, {int(q.sum())} of {len(q)} salient points, cell 0 = {grid[0]}")
+    path = os.path.join(out_dir, "arrange_hard.npz")
+    np.savez_compressed(path, **out)
+    print(f"hard: {os.path.getsize(path)} bytes -> {path}")
+    sys.stdout.flush()
+
+
 def time_child(lib):
     """The reference's own time for the inputs of tools/arrange_timing.py (this machine, one thread; context only)."""
     import importlib.util
@@ -291,19 +351,20 @@ def time_child(lib):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--time", action="store_true", help="only print the reference's CPU time for the inputs of tools/arrange_timing.py")
+    ap.add_argument("--hard", action="store_true", help="write arrange_hard.npz (the hostile cases of tests/hard_shapes.py) instead of the room fixtures")
     ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--child", nargs=2, default=None)
     a = ap.parse_args()
     if a.child:
-        return time_child(a.child[0]) if a.child[1] == "TIME" else child(a.child[0], a.out, a.child[1])
+        return time_child(a.child[0]) if a.child[1] == "TIME" else hard_child(a.child[0], a.out) if a.child[1] == "HARD" else child(a.child[0], a.out, a.child[1])
     here = os.path.dirname(os.path.abspath(__file__))
     with tempfile.TemporaryDirectory() as tmp:
         lib = os.path.join(tmp, "libarrfx.so")
         subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++11", "-fPIC", "-w", "-shared",
                                f"-I{a.ref}/lib", f"-I{a.ref}/lib/rs", f"-I{a.ref}/apps/pose_proposal", f"-I{a.ref}/apps/segment_transfer", "-o", lib,
                                os.path.join(here, "driver.cpp"), os.path.join(a.ref, "apps", "segment_transfer", "arrangement_optimization.cpp"), "-lm"])
-        for name in (["TIME"] if a.time else FIXTURES):
+        for name in (["TIME"] if a.time else ["HARD"] if a.hard else FIXTURES):
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, name, "--out", a.out], stdout=subprocess.PIPE, text=True)
             print("\n".join(ln for ln in r.stdout.splitlines() if not ln.startswith("RSAO_SALIENCY")))
             if r.returncode != 0:

@@ -1,6 +1,10 @@
 """Writes tests/golden/nms_<shape>.npz from the REFERENCE's own isect_get_overlap_factor and mgs_non_maxima_suppresion.
 
-    python tools/nms_fixture/gen.py [--ref /path/to/reference] [--out tests/golden]
+    python tools/nms_fixture/gen.py [--ref /path/to/reference] [--out tests/golden] [--hard]
+
+--hard writes tests/golden/isect_hard.npz instead: the hostile shapes of tests/hard_shapes.py (every family but "random"), their
+levels 1 and 3 given to the reference as they are (fx_shape_from_levels).  The clouds are not stored, only their lengths and CRCs.
+Cases the reference cannot run (a line of 4097 cells overruns its scanline arrays) are recorded with their expected refusal only.
 
 Run once, by hand, where the reference tree is available; no test runs it.  driver.cpp and the reference's
 pose_proposal.cpp are compiled into a temporary directory outside the tree (asserts on, -O2 -std=c++11, no -march, as
@@ -43,6 +47,8 @@ class Ref:
         L = self.L = C.CDLL(path)
         L.fx_shape_create.restype = C.c_void_p
         L.fx_shape_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.fx_shape_from_levels.restype = C.c_void_p
+        L.fx_shape_from_levels.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.fx_level.restype = C.c_int32
         L.fx_level.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.fx_centroid.argtypes = [C.c_void_p, C.c_void_p]
@@ -63,10 +69,19 @@ class Ref:
         self.L.fx_centroid(h, fp(c))
         return h, lv[1], lv[3], c
 
-    def overlap(self, h, pa, pb, voxel, inside, by_smaller):
+    def from_levels(self, l1, l3):
+        l1, l3 = np.ascontiguousarray(l1, F), np.ascontiguousarray(l3, F)
+        return self.L.fx_shape_from_levels(fp(l1), len(l1), fp(l3), len(l3))
+
+    def centroid(self, h):
+        c = np.zeros(3, F)
+        self.L.fx_centroid(h, fp(c))
+        return c
+
+    def overlap(self, h, pa, pb, voxel, inside, by_smaller, hb=None):
         pa, pb = np.ascontiguousarray(pa, F), np.ascontiguousarray(pb, F)
         cnt = np.zeros(3, np.int32)
-        ov = self.L.fx_overlap(h, fp(pa), h, fp(pb), F(voxel), inside, by_smaller, fp(cnt))
+        ov = self.L.fx_overlap(h, fp(pa), h if hb is None else hb, fp(pb), F(voxel), inside, by_smaller, fp(cnt))
         return F(ov), cnt
 
     def nms(self, h, poses, scores, thr):
@@ -212,25 +227,76 @@ def child(lib, out_dir):
     sys.stdout.flush()
 
 
+def hard_child(lib, out_dir):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_shapes as H
+    R = Ref(lib)
+    cases = H.fixture_cases()
+    case_first, shape_first, shape_crc = [0], [0], []
+    ia, ib, pa, pb, cnt, ov = [], [], [], [], [], []
+    warnings = 0
+    for c in cases:
+        hs = [R.from_levels(b, e) for b, e in c.shapes] if c.reference else []
+        for k in range(len(c)):
+            o, n = F(0.0), np.zeros(3, np.int32)
+            if c.reference:
+                o, n = R.overlap(hs[c.ia[k]], c.pose_a[k], c.pose_b[k], c.voxel, c.inside, c.by_smaller, hb=hs[c.ib[k]])
+                denom = min(n[0], n[1]) if c.by_smaller else max(n[0], n[1])
+                if denom == 0 and o == 1.0:                       # (a pair without a grid has overlap 0)
+                    assert c.name == "edges_empty", (c.name, k, "an empty grid outside the empty-boundary case")
+                    warnings += 1
+            ia.append(c.ia[k]); ib.append(c.ib[k]); pa.append(c.pose_a[k]); pb.append(c.pose_b[k]); cnt.append(n); ov.append(o)
+        case_first.append(len(ia)); shape_crc += list(c.crcs()); shape_first.append(len(shape_crc))
+        print(f"{c.name}: {len(c)} pairs, {len(c.shapes)} shapes, {'reference' if c.reference else 'expected refusal only: ' + c.expect}")
+    # the proposal list: the reference's own centroid, the threshold = one centroid distance's exact fp32 value
+    L = H.nms_list()
+    h = R.from_levels(*L["shape"])
+    cen = R.centroid(h)
+    i, j = L["decider"]
+    thr = H.centroid_distance(cen, L["poses"][i], L["poses"][j])
+    marks = R.nms(h, L["poses"], L["scores"], thr)
+    print(f"nms: {len(marks)} proposals, {int((marks == 1).sum())} kept, threshold {thr!r}")
+    out = dict(case_name=np.array([c.name for c in cases], "S24"), case_family=np.array([c.family for c in cases], "S8"),
+               case_expect=np.array([c.expect for c in cases], "S8"), case_reference=np.array([c.reference for c in cases], np.int32),
+               case_voxel=np.array([c.voxel for c in cases], F), case_inside=np.array([c.inside for c in cases], np.int32),
+               case_by_smaller=np.array([c.by_smaller for c in cases], np.int32), case_first=np.array(case_first, np.int32),
+               shape_first=np.array(shape_first, np.int32), shape_crc=np.array(shape_crc, np.int64).reshape(-1, 4),
+               shape_a=np.array(ia, np.int32), shape_b=np.array(ib, np.int32), pose_a=np.stack(pa).astype(F), pose_b=np.stack(pb).astype(F),
+               counts=np.stack(cnt).astype(np.int32), overlap=np.array(ov, F),
+               nms_shape_crc=np.array([len(L["shape"][0]), H.crc(L["shape"][0]), len(L["shape"][1]), H.crc(L["shape"][1])], np.int64),
+               nms_centroid=cen, nms_poses=L["poses"], nms_scores=L["scores"], nms_dist_threshold=F(thr), nms_marks=marks,
+               nms_decider=np.array(L["decider"], np.int32))
+    path = os.path.join(out_dir, "isect_hard.npz")
+    np.savez_compressed(path, **out)
+    print(f"{len(ia)} pairs in {len(cases)} cases, {os.path.getsize(path)} bytes -> {path}")
+    print(f"EXPECTED_WARNINGS {warnings}")
+    sys.stdout.flush()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--child", default=None)
+    ap.add_argument("--hard", action="store_true")
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.out)
+        return (hard_child if a.hard else child)(a.child, a.out)
     here = os.path.dirname(os.path.abspath(__file__))
     with tempfile.TemporaryDirectory() as tmp:
         lib = os.path.join(tmp, "libnmsfx.so")
         subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++11", "-fPIC", "-w", "-shared",
                                f"-I{a.ref}/lib", f"-I{a.ref}/lib/rs", f"-I{a.ref}/apps/pose_proposal", "-o", lib,
                                os.path.join(here, "driver.cpp"), os.path.join(a.ref, "apps", "pose_proposal", "pose_proposal.cpp"), "-lm"])
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, "--out", a.out], stdout=subprocess.PIPE, text=True)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, "--out", a.out] + (["--hard"] if a.hard else []), stdout=subprocess.PIPE, text=True)
         print(r.stdout, end="")
         if r.returncode != 0:
             raise SystemExit(f"generation failed (exit {r.returncode}: an assert of the reference or of this script)")
-        if "WARNING: Grid A count" in r.stdout:
+        if a.hard:
+            # the empty-grid warning is expected for the rows of the empty-boundary case and for nothing else
+            if f"EXPECTED_WARNINGS {r.stdout.count('WARNING: Grid A count')}\n" not in r.stdout:
+                raise SystemExit("the reference printed its empty-grid warning outside the empty-boundary case")
+        elif "WARNING: Grid A count" in r.stdout:
             raise SystemExit("the reference printed its empty-grid warning: the inputs do not meet the fixtures' condition")
 
 
