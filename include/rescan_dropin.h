@@ -134,6 +134,17 @@ int64_t rsd_compute_neighborhood( const rsd_vec3_t* pos, const rsd_vec3_t* nor, 
  * points within voxel_size, where a reference search would be truncated). */
 int32_t rsd_level_poisson( const rsd_vec3_t* pos, int32_t n, float voxel_size, int32_t level, int32_t* sample_idx );
 
+/* rs_pointcloud_uniform_resample (lib/rs/rs_pointcloud.h:1132-1227) on in_mesh's level 0 and faces_ind: the level-0 arrays of
+ * out_pc, bit for bit (qualities stay unset, as in the reference).  Returns the sample count — what the caller passes to
+ * rs_pointcloud__allocate_level — or a negative RS_HIP_E_* code with nothing written.  A call with every output NULL returns the
+ * count only and needs no device; otherwise pos is required, any other attribute with a NULL input or output is skipped, and
+ * `capacity` (the outputs' length in samples) below the count gives RS_HIP_E_ARG. */
+int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const rsd_vec3_t* col, const float* radii,
+                              const int32_t* class_ids, const int32_t* instance_ids, int64_t n_vertices,
+                              const int32_t* faces_ind, int64_t n_faces, int64_t capacity,
+                              rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_vec3_t* out_col, float* out_radii,
+                              int32_t* out_class, int32_t* out_instance );
+
 /* Scene-coverage term of the arrangement optimiser (apps/segment_transfer/arrangement_optimization.cpp:344-373).
  * rsd_coverage_create replaces isect_grid3d_init + rsao_rasterize_scene_to_grid for opts->scn_grd
  * (apps/segment_transfer/main.cpp:323-339); rsd_coverage_score replaces the body of

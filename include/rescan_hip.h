@@ -78,6 +78,10 @@ void            rs_hip_cloud_destroy( rs_hip_cloud_t* c );
 int32_t         rs_hip_cloud_size( const rs_hip_cloud_t* c );
 /* bytes of HBM held by the cloud */
 int64_t         rs_hip_cloud_bytes( const rs_hip_cloud_t* c );
+/* The cloud's points in the order they were given or produced: 3 * size floats each (either may be NULL; nor only of a cloud
+ * with normals).  A copy of what the cloud keeps on the host: no device work.  For clouds that were built on the device
+ * (rs_hip_cloud_create_level, rs_hip_cloud_create_resampled) this is how the caller sees their points. */
+int             rs_hip_cloud_points( const rs_hip_cloud_t* c, float* pos, float* nor );
 /* (diagnostics) Where cloud construction went, in seconds of the calling threads' wall clock, summed over every cloud the process
  * built since the last reset: out[0] host copy of the arrays, [1] upload + bounds, [2] cell index (sort by cell, offset table),
  * [3] Hilbert order + tiles.  Returns the number of clouds counted; reset != 0 clears the counters. */
@@ -380,6 +384,49 @@ rs_hip_cloud_t* rs_hip_cloud_create_level( const rs_hip_cloud_t* base, float rad
  * class and instance ids), dst[a][i] = src[a][sample_idx[i]].  Entries with a NULL src or dst are skipped. */
 int rs_hip_gather_attributes( const int32_t* sample_idx, int32_t count, int32_t n_src,
                               const void* const* src, const int32_t* words, void* const* dst, int32_t n_arrays );
+
+/* ---- mesh resampler: the level-0 cloud of a mesh ---------------------------- */
+
+/* rs_pointcloud_uniform_resample (lib/rs/rs_pointcloud.h:1132-1227), the call rs_pointcloud_from_files sends every PLY
+ * with faces through (:1268-1276), bit for bit: positions, normals, colours, radii, class and instance ids of the
+ * n_samples = (size_t)( 0.5 * total_area * 12800.0 ) samples.  The reference threads two PCG32 generators
+ * (lib/msh/msh_std.h:1413-1470; seeds 12346 for the barycentric draws, 64321 for the alias sampler) through its loop and
+ * takes exactly two draws from each per sample, so sample i is computed on its own from the states 2 i steps after the
+ * seeding.  Face areas (:1143-1154; msh_vec3_cross / msh_vec3_norm, msh_vec_math.h:974,988), their double sum, the sample
+ * count and the alias table (msh_distrib2pdf + msh_discrete_distribution_update, msh_std.h:1843-1849,1863-1925 — with
+ * the normaliser msh_accumulated rounds to float) are made on the host; the samples on the device.  Qualities, which the
+ * reference leaves unset, are not an output.
+ *
+ * Refusals, all decided on the host before any launch (rs_hip_last_error() says which):
+ *   RS_HIP_E_ARG       a vertex index outside [0, n_vertices); n_faces <= 0; a total area that is not finite; an fp32 area
+ *                      sum <= 1e-8 (the reference then samples from an uninitialised pdf, msh_std.h:1846)
+ *   RS_HIP_E_CAPACITY  n_faces > 2^24 (beyond it (float)n_faces is inexact and the reference's alias column can reach
+ *                      n_faces); n_samples > INT32_MAX
+ *
+ * pos: 3 * n_vertices floats; faces: 3 * n_faces vertex indices. */
+
+/* The host part alone; needs no device.  n_samples, total_area (the double sum), and the alias table: prob / alias
+ * (each may be NULL, n_faces entries).  An alias entry the reference never writes (its prob is 1.0) holds its own index. */
+int rs_hip_resample_plan( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                          int64_t* n_samples, double* total_area,
+                          double* prob /* may be NULL, n_faces */, int32_t* alias /* may be NULL, n_faces */ );
+
+/* Samples first .. first + count - 1 of the reference's sequence; host pointers in and out.  An attribute whose input or
+ * output pointer is NULL is skipped; pos and out_pos are required.  The window must lie inside [0, n_samples]
+ * (RS_HIP_E_ARG otherwise); count = 0 succeeds and writes nothing.  out_face (may be NULL): the face each sample lies on.
+ * A sample does not depend on the window it is asked for in, so windows that partition [0, n_samples) give the whole
+ * sequence.  A normal whose interpolated sum is zero is NaN, as in the reference (1 / sqrtf( 0 ) times 0). */
+int rs_hip_uniform_resample( const float* pos, const float* nor, const float* col, const float* radii,
+                             const int32_t* class_ids, const int32_t* instance_ids, int64_t n_vertices,
+                             const int32_t* faces, int64_t n_faces, int64_t first, int64_t count,
+                             float* out_pos, float* out_nor, float* out_col, float* out_radii,
+                             int32_t* out_class, int32_t* out_instance, int32_t* out_face /* may be NULL */ );
+
+/* The whole level-0 cloud, sampled and indexed without leaving the device: the samples' positions (and normals, where
+ * nor is not NULL) are written where the index build of rs_hip_cloud_create_level reads them (cell_size as for
+ * rs_hip_cloud_create).  n_samples may be NULL.  NULL on failure; rs_hip_cloud_points hands the points to the host. */
+rs_hip_cloud_t* rs_hip_cloud_create_resampled( const float* pos, const float* nor, int64_t n_vertices,
+                                               const int32_t* faces, int64_t n_faces, float cell_size, int64_t* n_samples );
 
 /* ---- neighbourhood graph ------------------------------------------ */
 

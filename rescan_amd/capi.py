@@ -100,6 +100,10 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "rs_hip_cloud_create_level": (C.c_void_p, [C.c_void_p, C.c_float, C.c_int32, C.c_float, i32p, C.POINTER(C.c_int32)]),
     "rs_hip_level_samples": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rs_hip_cloud_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_resample_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "rs_hip_uniform_resample": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7),
+    "rs_hip_cloud_create_resampled": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.POINTER(C.c_int64)]),
     "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rs_hip_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
@@ -243,6 +247,25 @@ class Cloud:
         self._nor = None if base._nor is None else base._nor[idx]
         return self, idx
 
+    @classmethod
+    def resampled(cls, pos, nor, faces, cell_size=-1.0):
+        """The level-0 cloud of a mesh (rs_pointcloud_uniform_resample), sampled and indexed on the device
+        (rs_hip_cloud_create_resampled).  nor may be None."""
+        lib = load()
+        pos = _f32(pos).reshape(-1, 3); faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        nor = None if nor is None else _f32(nor).reshape(-1, 3)
+        n = C.c_int64()
+        h = lib.rs_hip_cloud_create_resampled(pos.ctypes.data, None if nor is None else nor.ctypes.data, len(pos),
+                                              faces.ctypes.data, len(faces), float(cell_size), C.byref(n))
+        if not h:
+            raise RescanHipError("rs_hip_cloud_create_resampled failed: " + lib.rs_hip_last_error().decode())
+        self = cls.__new__(cls)
+        self.handle = h; self.n = n.value
+        self._pos = np.zeros((self.n, 3), np.float32)
+        self._nor = None if nor is None else np.zeros((self.n, 3), np.float32)
+        _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, None if nor is None else self._nor.ctypes.data))
+        return self
+
     @property
     def nbytes(self):
         return load().rs_hip_cloud_bytes(self.handle)
@@ -267,6 +290,44 @@ def radius_search(target, query, radius, k):
     tot = C.c_uint64()
     _check(load().rs_hip_radius_search(target.handle, query, nq, float(radius), int(k), d, i, nn, C.byref(tot)))
     return d, i, nn.astype(np.int64), tot.value
+
+
+def resample_plan(pos, faces, table=True):
+    """The host part of the mesh resampler (rs_hip_resample_plan; no device needed): (n_samples, total_area, prob, alias), the
+    last two None when table is False."""
+    pos = _f32(pos).reshape(-1, 3); faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    n, total = C.c_int64(), C.c_double()
+    prob = np.zeros(len(faces), np.float64) if table else None
+    alias = np.zeros(len(faces), np.int32) if table else None
+    _check(load().rs_hip_resample_plan(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces), C.byref(n), C.byref(total),
+                                       prob.ctypes.data if table else None, alias.ctypes.data if table else None))
+    return n.value, total.value, prob, alias
+
+
+def uniform_resample(pos, faces, nor=None, col=None, radii=None, class_ids=None, instance_ids=None, first=0, count=None):
+    """rs_pointcloud_uniform_resample on the device: samples first .. first + count - 1 of the reference's sequence (count None: to
+    the end).  Returns a dict: n_samples, pos, face, and nor / col / radii / class_ids / instance_ids for the attributes given."""
+    pos = _f32(pos).reshape(-1, 3); faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    n_samples = resample_plan(pos, faces, table=False)[0]
+    if count is None:
+        count = n_samples - first
+    ins = dict(nor=None if nor is None else _f32(nor).reshape(-1, 3), col=None if col is None else _f32(col).reshape(-1, 3),
+               radii=None if radii is None else _f32(radii).ravel(),
+               class_ids=None if class_ids is None else np.ascontiguousarray(class_ids, np.int32).ravel(),
+               instance_ids=None if instance_ids is None else np.ascontiguousarray(instance_ids, np.int32).ravel())
+    m = max(int(count), 0)
+    out = dict(n_samples=n_samples, pos=np.zeros((m, 3), np.float32), face=np.zeros(m, np.int32))
+    for k, v in ins.items():
+        if v is not None:
+            if len(v) != len(pos):
+                raise ValueError(f"{k}: one entry per vertex")
+            out[k] = np.zeros((m, 3), np.float32) if v.ndim == 2 else np.zeros(m, v.dtype)
+    ptr = lambda a: None if a is None else a.ctypes.data        # noqa: E731
+    _check(load().rs_hip_uniform_resample(pos.ctypes.data, *[ptr(ins[k]) for k in ("nor", "col", "radii", "class_ids", "instance_ids")],
+                                          len(pos), faces.ctypes.data, len(faces), int(first), int(count), out["pos"].ctypes.data,
+                                          *[ptr(out.get(k)) for k in ("nor", "col", "radii", "class_ids", "instance_ids")],
+                                          out["face"].ctypes.data))
+    return out
 
 
 KNN_MAX_K = 64          # RS_HIP_KNN_MAX_K

@@ -784,6 +784,14 @@ rs_hip_cloud_t* rs_hip_cloud_create( const float* pos, const float* nor, int32_t
   return cloud_create_impl( pos, nor, n, cell_size, false );
 }
 
+int rs_hip_cloud_points( const rs_hip_cloud_t* c, float* pos, float* nor )
+{
+  if( !c || ( nor && !c->has_nor ) ) { set_err( "cloud_points: no cloud, or normals asked of a cloud without them" ); return RS_HIP_E_ARG; }
+  if( pos ) std::memcpy( pos, c->h_pos.data(), c->h_pos.size() * 4 );
+  if( nor ) std::memcpy( nor, c->h_nor.data(), c->h_nor.size() * 4 );
+  return RS_HIP_OK;
+}
+
 void rs_hip_cloud_destroy( rs_hip_cloud_t* c )
 {
   if( !c ) return;
@@ -2700,4 +2708,16 @@ void api_set_err( const char* what ) { set_err( "%s", what ); }
 const GridView* api_cloud_view( const rs_hip_cloud* c ) { return c ? &c->view : nullptr; }
 void* api_prof_begin() { return g_prof ? (void*)prof_event() : nullptr; }
 void api_prof_end( const char* name, void* begin ) { if( begin ) prof_span( name, (hipEvent_t)begin, prof_event() ); }
+int api_level_workspace( size_t n, bool with_nor, float** pos, float** nor )
+{
+  int rc = ensure_ready(); if( rc ) return rc;
+  const size_t nn = std::max<size_t>( 1, n );
+  if( ( rc = g_ws.lvl_pos.ensure( nn * 12 ) ) || ( with_nor && ( rc = g_ws.lvl_nor.ensure( nn * 12 ) ) ) ) return rc;
+  *pos = g_ws.lvl_pos.as<float>(); *nor = with_nor ? g_ws.lvl_nor.as<float>() : nullptr;
+  return RS_HIP_OK;
+}
+rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float cell_size )
+{
+  return cloud_create_impl( g_ws.lvl_pos.as<float>(), with_nor ? g_ws.lvl_nor.as<float>() : nullptr, n, cell_size, true );
+}
 } // namespace rs

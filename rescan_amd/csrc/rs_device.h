@@ -373,5 +373,9 @@ void            api_set_err( const char* what );           // rs_hip_last_error(
 const GridView* api_cloud_view( const struct ::rs_hip_cloud* c );
 void*           api_prof_begin();                          // rs_hip_profile_enable: an event on the thread's stream (null: profiling off)
 void            api_prof_end( const char* name, void* begin );   // ... and the span since then, booked under `name`
+// the level builder's gather target, for a producer in another unit (rs_mesh.hip): room for n points (normals: *nor, else null) ...
+int             api_level_workspace( size_t n, bool with_nor, float** pos, float** nor );
+// ... and the cloud over the n points written there (the index build of rs_hip_cloud_create_level); null on failure
+struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float cell_size );
 
 } // namespace rs

@@ -868,6 +868,24 @@ int32_t rsd_level_poisson( const rsd_vec3_t* pos, int32_t n, float voxel_size, i
   return n_samples;
 }
 
+int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const rsd_vec3_t* col, const float* radii,
+                              const int32_t* class_ids, const int32_t* instance_ids, int64_t n_vertices,
+                              const int32_t* faces_ind, int64_t n_faces, int64_t capacity,
+                              rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_vec3_t* out_col, float* out_radii,
+                              int32_t* out_class, int32_t* out_instance )
+{
+  int64_t n_samples = 0;
+  int rc = rs_hip_resample_plan( (const float*)pos, n_vertices, faces_ind, n_faces, &n_samples, nullptr, nullptr, nullptr );
+  if( rc ) { complain( "uniform_resample" ); return rc; }
+  if( !out_pos && !out_nor && !out_col && !out_radii && !out_class && !out_instance ) return n_samples;
+  if( capacity < n_samples ) { fprintf( stderr, "rescan_dropin: uniform_resample: capacity %lld below the %lld samples\n", (long long)capacity, (long long)n_samples ); return RS_HIP_E_ARG; }
+  rc = rs_hip_uniform_resample( (const float*)pos, (const float*)nor, (const float*)col, radii, class_ids, instance_ids, n_vertices,
+                                faces_ind, n_faces, 0, n_samples, (float*)out_pos, (float*)out_nor, (float*)out_col, out_radii,
+                                out_class, out_instance, nullptr );
+  if( rc ) { complain( "uniform_resample" ); return rc; }
+  return n_samples;
+}
+
 void* rsd_coverage_create( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
                            const rsd_vec3_t* scene_pos, const float* scene_quality, int32_t n_scene, float quality_threshold )
 {
