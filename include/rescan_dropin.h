@@ -145,6 +145,21 @@ int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, cons
                               rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_vec3_t* out_col, float* out_radii,
                               int32_t* out_class, int32_t* out_instance );
 
+/* The body of rsdu_augment_database's `if( extracted_shape )` block (apps/segment_transfer/database_update.cpp:58-90) for one
+ * placement, extraction included: the points of input_scan's level 1 that carry uidx, aligned to cur_shape's level 0 by icp_align
+ * ( .., 0.05, msh_deg2rad( 10 ) ) from inverse( pose ) unless is_static, transformed, merged with cur_shape and shuffled — the level-0
+ * arrays of merged_shape, allocated with malloc (rs_pointcloud_free releases them), every instance id set to uidx.  The model's
+ * instance ids are not an input: the reference overwrites them.  xform (may be NULL): the pose the points were moved by.  Returns the
+ * merged count; 0 with nothing allocated when no scan point carries uidx (the reference then leaves the object as it is); a negative
+ * RS_HIP_E_* code on failure.  Bit for bit the reference's arrays up to 16 384 extracted points (include/rescan_hip.h). */
+int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_nor, const rsd_vec3_t* scan_col, const float* scan_radii,
+                           const float* scan_qual, const int32_t* scan_class, const int32_t* scan_instance, int32_t n_scan,
+                           const rsd_vec3_t* model_pos, const rsd_vec3_t* model_nor, const rsd_vec3_t* model_col, const float* model_radii,
+                           const float* model_qual, const int32_t* model_class, int32_t n_model,
+                           const rsd_mat4_t* pose, int32_t uidx, int32_t is_static,
+                           rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
+                           int32_t** out_class, int32_t** out_instance, rsd_mat4_t* xform );
+
 /* Scene-coverage term of the arrangement optimiser (apps/segment_transfer/arrangement_optimization.cpp:344-373).
  * rsd_coverage_create replaces isect_grid3d_init + rsao_rasterize_scene_to_grid for opts->scn_grd
  * (apps/segment_transfer/main.cpp:323-339); rsd_coverage_score replaces the body of

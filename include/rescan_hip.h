@@ -428,6 +428,66 @@ int rs_hip_uniform_resample( const float* pos, const float* nor, const float* co
 rs_hip_cloud_t* rs_hip_cloud_create_resampled( const float* pos, const float* nor, int64_t n_vertices,
                                                const int32_t* faces, int64_t n_faces, float cell_size, int64_t* n_samples );
 
+/* ---- model fusion: the row that closes a timestep ------------------------- */
+
+/* rsdu_augment_database (apps/segment_transfer/database_update.cpp:22-91) for one placement: the scan's points that carry
+ * the placement's instance id (rs_pointcloud_copy_by_ids, lib/rs/rs_pointcloud.h:239-297), aligned to the object's level-0
+ * model by icp_align( .., 0.05, 10 deg ) from inverse( pose ) unless the object is static, moved into the model's frame
+ * (rs_pointcloud_transform, :1367-1378), concatenated with the model and shuffled by the Fisher-Yates pass of
+ * rs_pointcloud_merge (:383-446; PCG32, seed 12346).  Bit for bit wherever the ICP pose is: the library's ICP runs in the
+ * reference's order up to 16 384 source points; above that its pose is within 1e-4 of the reference's, and the merged
+ * positions of such an object inherit that difference.
+ *
+ * Refusals, all decided on the host before any launch (rs_hip_last_error() says which):
+ *   RS_HIP_E_ARG       a negative count; a required array that is NULL; an id listed twice (the reference would emit
+ *                      its points once per entry); a cloud without normals
+ *   RS_HIP_E_CAPACITY  more than 2^24 merged points: up to there (float)i is exact and the shuffle's j < i for every
+ *                      draw; beyond it the reference's j can exceed i */
+
+/* The shuffle's permutation, made by the reference's loop on the host; needs no device.  perm[i] (n entries): the index,
+ * in the concatenation "A then B", of the element that ends at position i.  n = 0 and n = 1 succeed. */
+int rs_hip_shuffle_plan( int64_t n, uint32_t seed, int32_t* perm );
+
+/* The same array made on the device: every step's draw by jumping the generator ahead, a sort of the steps by the
+ * position they target, and one walk per output position (rs_fuse.hip). */
+int rs_hip_shuffle_permutation( int64_t n, uint32_t seed, int32_t* perm );
+
+/* index[0 .. *count): the i, increasing, with point_ids[i] among the n_ids entries of ids — the order
+ * rs_pointcloud_copy_by_ids emits.  Host pointers in and out; index has room for n entries.  A count of 0 is no error. */
+int rs_hip_select_by_ids( const int32_t* point_ids, int64_t n, const int32_t* ids, int32_t n_ids, int32_t* index, int64_t* count );
+
+/* The merge stage alone on host arrays, with the pose given: A's points and normals through xform (msh_mat4_vec3_mul,
+ * points with w = 1, normals with w = 0, not renormalised), then B's as they are, shuffled.  out_pos / out_nor:
+ * 3 * (n_a + n_b) floats; source (may be NULL, n_a + n_b entries): source[i] < n_a names A's point, otherwise B's point
+ * source[i] - n_a — the permutation of rs_hip_shuffle_plan.  Either count may be 0. */
+int rs_hip_merge_shuffled( const float* a_pos, const float* a_nor, int64_t n_a, const float xform[16],
+                           const float* b_pos, const float* b_nor, int64_t n_b, uint32_t seed,
+                           float* out_pos, float* out_nor, int32_t* source /* may be NULL */ );
+
+/* The whole row without leaving the device: the merged level-0 cloud, indexed (cell_size as for rs_hip_cloud_create);
+ * rs_hip_cloud_create_level builds its levels and rs_hip_cloud_points hands its points to the host.
+ *   scan, scan_instance_ids   the scan's level-1 cloud and one id per point, in the order the points were given to it
+ *   uidx                      the placement's instance id
+ *   model, pose               the object's level-0 cloud and the placement's pose; xform = rs_hip_mat4_inverse( pose )
+ *   refine                    0 for a static object; otherwise rs_hip_icp_align( extracted, model, xform, identity,
+ *                             max_dist, max_angle, 100 iterations ) — the reference passes 0.05 and 10 degrees
+ * Out, each may be NULL: xform_out, the pose used; icp_err, what the ICP returned (0 without it); source, as for
+ * rs_hip_merge_shuffled (n_extracted + the model's size entries); scan_index (room for the scan's size), the scan point
+ * behind extracted point k; n_extracted.  The other attributes follow on the host through source / scan_index and
+ * rs_hip_gather_attributes; the instance ids of the result are all uidx (database_update.cpp:79-85).
+ * No point carries uidx: NULL with rs_hip_last_error() empty and *n_extracted = 0 — the reference leaves the model as it
+ * is (database_update.cpp:58).  NULL with a message on failure. */
+rs_hip_cloud_t* rs_hip_cloud_create_fused( const rs_hip_cloud_t* scan, const int32_t* scan_instance_ids, int32_t uidx,
+                                           const rs_hip_cloud_t* model, const float pose[16], int32_t refine,
+                                           float max_dist, float max_angle, float cell_size,
+                                           float xform_out[16], float* icp_err, int32_t* source, int32_t* scan_index,
+                                           int64_t* n_extracted );
+
+/* Diagnostics: where rs_hip_cloud_create_fused's time went on the calling thread since the last call of this function —
+ * extraction | ICP | permutation | merge | index build, seconds (out may be NULL) — and whether the next calls keep the
+ * clock (enable != 0: they then synchronise after every stage). */
+void rs_hip_fuse_seconds( double out[5], int32_t enable );
+
 /* ---- neighbourhood graph ------------------------------------------ */
 
 /* rspf_compute_neighborhood (lib/rs/rs_pointcloud_filters.cpp:674-722): K = max_nn self-search

@@ -104,6 +104,14 @@ SIGNATURES = {
     "rs_hip_resample_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "rs_hip_uniform_resample": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7),
     "rs_hip_cloud_create_resampled": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.POINTER(C.c_int64)]),
+    "rs_hip_shuffle_plan": (C.c_int, [C.c_int64, C.c_uint32, C.c_void_p]),
+    "rs_hip_shuffle_permutation": (C.c_int, [C.c_int64, C.c_uint32, C.c_void_p]),
+    "rs_hip_select_by_ids": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
+    "rs_hip_merge_shuffled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_cloud_create_fused": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float,
+                                               C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "rs_hip_fuse_seconds": (None, [C.c_void_p, C.c_int32]),
     "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rs_hip_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
@@ -266,6 +274,38 @@ class Cloud:
         _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, None if nor is None else self._nor.ctypes.data))
         return self
 
+    @classmethod
+    def fused(cls, scan, scan_instance_ids, uidx, model, pose, refine=True, max_dist=0.05, max_angle=np.float32(10.0 * 0.005555555556 * np.pi),
+              cell_size=-1.0):
+        """One placement of rsdu_augment_database on the device (rs_hip_cloud_create_fused): the scan's points with instance id
+        uidx, aligned to `model` from inverse(pose) when refine, moved into the model's frame, merged with it and shuffled.
+        Returns (cloud, info) with info = dict(xform, icp_err, source, scan_index, n_extracted); source[i] < n_extracted names
+        extracted point source[i] (scan point scan_index[source[i]]), otherwise model point source[i] - n_extracted.
+        (None, info) when no point carries uidx."""
+        lib = load()
+        ids = np.ascontiguousarray(scan_instance_ids, np.int32).ravel()
+        if len(ids) != scan.n:
+            raise ValueError("scan_instance_ids: one entry per scan point")
+        pose = _f32(pose).ravel()
+        xform = np.zeros(16, np.float32); err = C.c_float(); n_ext = C.c_int64()
+        source = np.zeros(scan.n + model.n, np.int32); scan_index = np.zeros(max(scan.n, 1), np.int32)
+        h = lib.rs_hip_cloud_create_fused(scan.handle, ids.ctypes.data, int(uidx), model.handle, pose.ctypes.data, int(bool(refine)),
+                                          float(max_dist), float(max_angle), float(cell_size), xform.ctypes.data, C.byref(err),
+                                          source.ctypes.data, scan_index.ctypes.data, C.byref(n_ext))
+        na = n_ext.value
+        info = dict(xform=xform, icp_err=err.value, source=source[:na + model.n if h else 0].copy(), scan_index=scan_index[:na].copy(),
+                    n_extracted=na)
+        if not h:
+            msg = lib.rs_hip_last_error().decode()
+            if msg:
+                raise RescanHipError("rs_hip_cloud_create_fused failed: " + msg)
+            return None, info
+        self = cls.__new__(cls)
+        self.handle = h; self.n = na + model.n
+        self._pos = np.zeros((self.n, 3), np.float32); self._nor = np.zeros((self.n, 3), np.float32)
+        _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, self._nor.ctypes.data))
+        return self, info
+
     @property
     def nbytes(self):
         return load().rs_hip_cloud_bytes(self.handle)
@@ -327,6 +367,53 @@ def uniform_resample(pos, faces, nor=None, col=None, radii=None, class_ids=None,
                                           len(pos), faces.ctypes.data, len(faces), int(first), int(count), out["pos"].ctypes.data,
                                           *[ptr(out.get(k)) for k in ("nor", "col", "radii", "class_ids", "instance_ids")],
                                           out["face"].ctypes.data))
+    return out
+
+
+SEED_MERGE = 12346      # rs_pointcloud_merge's shuffle (lib/rs/rs_pointcloud.h:428)
+
+
+def shuffle_plan(n, seed=SEED_MERGE):
+    """The permutation of rs_pointcloud_merge's shuffle over n elements, by the reference's loop on the host
+    (rs_hip_shuffle_plan; no device needed): perm[i] = the index in "A then B" of the element that ends at i."""
+    perm = np.zeros(max(int(n), 0), np.int32)
+    _check(load().rs_hip_shuffle_plan(int(n), int(seed), perm.ctypes.data))
+    return perm
+
+
+def shuffle_permutation(n, seed=SEED_MERGE):
+    """The same permutation made on the device (rs_hip_shuffle_permutation)."""
+    perm = np.zeros(max(int(n), 0), np.int32)
+    _check(load().rs_hip_shuffle_permutation(int(n), int(seed), perm.ctypes.data))
+    return perm
+
+
+def select_by_ids(point_ids, ids):
+    """rs_pointcloud_copy_by_ids' selection (rs_hip_select_by_ids): the indices i, increasing, with point_ids[i] in ids."""
+    point_ids = np.ascontiguousarray(point_ids, np.int32).ravel(); ids = np.ascontiguousarray(ids, np.int32).ravel()
+    index = np.zeros(max(len(point_ids), 1), np.int32); count = C.c_int64()
+    _check(load().rs_hip_select_by_ids(point_ids.ctypes.data, len(point_ids), ids.ctypes.data, len(ids), index.ctypes.data, C.byref(count)))
+    return index[:count.value].copy()
+
+
+def merge_shuffled(a_pos, a_nor, xform, b_pos, b_nor, seed=SEED_MERGE):
+    """rs_pointcloud_transform of A by xform, then rs_pointcloud_merge( A, B ) (rs_hip_merge_shuffled): (pos, nor, source)."""
+    a_pos = _f32(a_pos).reshape(-1, 3); a_nor = _f32(a_nor).reshape(-1, 3); b_pos = _f32(b_pos).reshape(-1, 3); b_nor = _f32(b_nor).reshape(-1, 3)
+    if len(a_nor) != len(a_pos) or len(b_nor) != len(b_pos):
+        raise ValueError("one normal per point")
+    xform = _f32(xform).ravel()
+    n = len(a_pos) + len(b_pos)
+    pos = np.zeros((n, 3), np.float32); nor = np.zeros((n, 3), np.float32); source = np.zeros(n, np.int32)
+    _check(load().rs_hip_merge_shuffled(a_pos.ctypes.data, a_nor.ctypes.data, len(a_pos), xform.ctypes.data, b_pos.ctypes.data, b_nor.ctypes.data,
+                                        len(b_pos), int(seed), pos.ctypes.data, nor.ctypes.data, source.ctypes.data))
+    return pos, nor, source
+
+
+def fuse_seconds(enable=True):
+    """rs_hip_fuse_seconds: (extraction, ICP, permutation, merge, index build) seconds of Cloud.fused on this thread since the
+    last call; enable: whether the next calls keep the clock."""
+    out = np.zeros(5, np.float64)
+    load().rs_hip_fuse_seconds(out.ctypes.data, int(bool(enable)))
     return out
 
 

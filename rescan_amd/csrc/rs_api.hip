@@ -2720,4 +2720,8 @@ rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float ce
 {
   return cloud_create_impl( g_ws.lvl_pos.as<float>(), with_nor ? g_ws.lvl_nor.as<float>() : nullptr, n, cell_size, true );
 }
+CloudPoints api_cloud_points( const rs_hip_cloud* c )
+{
+  return CloudPoints{ c->d_qpos, c->has_nor ? c->d_qnor : nullptr, c->d_qby_orig, c->n };
+}
 } // namespace rs

@@ -377,5 +377,9 @@ void            api_prof_end( const char* name, void* begin );   // ... and the 
 int             api_level_workspace( size_t n, bool with_nor, float** pos, float** nor );
 // ... and the cloud over the n points written there (the index build of rs_hip_cloud_create_level); null on failure
 struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float cell_size );
+// a cloud's points for a reader in another unit (rs_fuse.hip): the query layout (Hilbert order, 16-byte records) and the map from an
+// original index to its slot there; nor is null for a cloud without normals
+struct CloudPoints { const float4* qpos; const float4* qnor; const int* by_orig; int n; };
+CloudPoints     api_cloud_points( const struct ::rs_hip_cloud* c );
 
 } // namespace rs

@@ -886,6 +886,51 @@ int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, cons
   return n_samples;
 }
 
+int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_nor, const rsd_vec3_t* scan_col, const float* scan_radii,
+                           const float* scan_qual, const int32_t* scan_class, const int32_t* scan_instance, int32_t n_scan,
+                           const rsd_vec3_t* model_pos, const rsd_vec3_t* model_nor, const rsd_vec3_t* model_col, const float* model_radii,
+                           const float* model_qual, const int32_t* model_class, int32_t n_model,
+                           const rsd_mat4_t* pose, int32_t uidx, int32_t is_static,
+                           rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
+                           int32_t** out_class, int32_t** out_instance, rsd_mat4_t* xform )
+{
+  if( !scan_pos || !scan_nor || !scan_col || !scan_radii || !scan_qual || !scan_class || !scan_instance || n_scan < 0 || n_model < 0 ||
+      ( n_model > 0 && ( !model_pos || !model_nor || !model_col || !model_radii || !model_qual || !model_class ) ) || !pose ||
+      !out_pos || !out_nor || !out_col || !out_radii || !out_qual || !out_class || !out_instance )
+  { fprintf( stderr, "rescan_dropin: augment_model: null arrays or a negative count\n" ); return RS_HIP_E_ARG; }
+  const CloudRef scan = cached_cloud( scan_pos, scan_nor, n_scan, -1.0f );
+  const CloudRef model = cached_cloud( model_pos, model_nor, n_model, -1.0f );
+  if( !scan || !model ) return RS_HIP_E_RUNTIME;
+  std::vector<int32_t> source( (size_t)n_scan + (size_t)n_model ), scan_index( (size_t)( n_scan > 0 ? n_scan : 1 ) );
+  int64_t n_a = 0; float err = 0.0f; rsd_mat4_t x;
+  const float max_angle = (float)( 10.0f * 0.005555555556 * 3.1415926535897932384626433832 );       // msh_deg2rad( 10.0f ), msh_std.h:618,625
+  rs_hip_cloud_t* merged = rs_hip_cloud_create_fused( scan.get(), scan_instance, uidx, model.get(), pose->data, is_static ? 0 : 1, 0.05f, max_angle,
+                                                      -1.0f, x.data, &err, source.data(), scan_index.data(), &n_a );
+  if( !merged )
+  {
+    if( rs_hip_last_error()[0] ) { complain( "augment_model" ); return RS_HIP_E_RUNTIME; }
+    return 0;                                              // no point carries uidx: the model stays (database_update.cpp:58)
+  }
+  const size_t n = (size_t)n_a + (size_t)n_model;
+  rsd_vec3_t* p = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) ); rsd_vec3_t* q = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) );
+  rsd_vec3_t* c = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) );
+  float* r = (float*)malloc( n * sizeof(float) ); float* ql = (float*)malloc( n * sizeof(float) );
+  int32_t* cl = (int32_t*)malloc( n * sizeof(int32_t) ); int32_t* in = (int32_t*)malloc( n * sizeof(int32_t) );
+  const int rc = ( p && q && c && r && ql && cl && in ) ? rs_hip_cloud_points( merged, (float*)p, (float*)q ) : RS_HIP_E_RUNTIME;
+  rs_hip_cloud_destroy( merged );
+  if( rc ) { free( p ); free( q ); free( c ); free( r ); free( ql ); free( cl ); free( in ); complain( "augment_model" ); return RS_HIP_E_RUNTIME; }
+  for( size_t i = 0; i < n; ++i )
+  {
+    const int32_t s = source[i];
+    if( s < n_a ) { const int32_t k = scan_index[(size_t)s]; c[i] = scan_col[k]; r[i] = scan_radii[k]; ql[i] = scan_qual[k]; cl[i] = scan_class[k]; }
+    else { const size_t k = (size_t)( s - n_a ); c[i] = model_col[k]; r[i] = model_radii[k]; ql[i] = model_qual[k]; cl[i] = model_class[k]; }
+    in[i] = uidx;                                          // database_update.cpp:79-85
+  }
+  *out_pos = p; *out_nor = q; *out_col = c; *out_radii = r; *out_qual = ql; *out_class = cl; *out_instance = in;
+  if( xform ) *xform = x;
+  return (int64_t)n;
+}
+
 void* rsd_coverage_create( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
                            const rsd_vec3_t* scene_pos, const float* scene_quality, int32_t n_scene, float quality_threshold )
 {
