@@ -160,6 +160,31 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
                            rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
                            int32_t** out_class, int32_t** out_instance, rsd_mat4_t* xform );
 
+/* The plane stage of segment_transfer (lib/rs/rs_pointcloud_filters.cpp), on host arrays as the reference holds them.  A plane
+ * model crosses as plain arrays, model m at centers[m], normals[m], axes[9m] (msh_mat3_t's data: column-major), extends[4m]
+ * (msh_vec4_t's x, y, z, w), valid[m], normal_up_dot[m] = features.normal_up_dot (include/rescan_hip.h).  INTEGRATION.md §3 has
+ * the patches.
+ *
+ * rsd_detect_floor_and_walls replaces rspf__detect_floor + rspf__detect_walls (:506-507) on pc's level 2: the models they push, in
+ * their order, n_inliers = each one's votes, *n_floors / *n_walls their return values.  Returns the number of models (<= capacity),
+ * or a negative RS_HIP_E_* code with nothing written (include/rescan_hip.h lists the refusals).
+ *
+ * rsd_gather_model_inliers replaces rspf__gather_model_inliers (:517, :640): *index = one malloc'ed array (the caller frees it) with
+ * model m's inlier indices, increasing, at [offsets[m], offsets[m + 1]); offsets has n_models + 1 entries.  Returns the total, or a
+ * negative code with *index = NULL.
+ *
+ * rsd_relabel_walls_and_floors replaces the gather and the loop of rspf_relabel_walls_and_floors (:632-667) on pc's level 1:
+ * class_ids / instance_ids are rewritten in place.  0, or a negative code with both arrays as they were. */
+int32_t rsd_detect_floor_and_walls( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, float dot_threshold, float dist_threshold,
+                                    int64_t count_threshold, int32_t capacity, rsd_vec3_t* centers, rsd_vec3_t* normals, int64_t* n_inliers,
+                                    int32_t* n_floors, int32_t* n_walls );
+int64_t rsd_gather_model_inliers( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, const rsd_vec3_t* centers, const rsd_vec3_t* normals,
+                                  const float* axes, const float* extends, const int8_t* valid, int32_t n_models, float dot_threshold,
+                                  float dist_threshold, int32_t check_validity, int32_t check_extends, int32_t** index, int64_t* offsets );
+int     rsd_relabel_walls_and_floors( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, const rsd_vec3_t* centers, const rsd_vec3_t* normals,
+                                      const float* axes, const float* extends, const int8_t* valid, const float* normal_up_dot, int32_t n_models,
+                                      int32_t floor_idx, int32_t wall_idx, int32_t unlabelled_idx, int32_t* class_ids, int32_t* instance_ids );
+
 /* Scene-coverage term of the arrangement optimiser (apps/segment_transfer/arrangement_optimization.cpp:344-373).
  * rsd_coverage_create replaces isect_grid3d_init + rsao_rasterize_scene_to_grid for opts->scn_grd
  * (apps/segment_transfer/main.cpp:323-339); rsd_coverage_score replaces the body of

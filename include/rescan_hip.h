@@ -611,6 +611,85 @@ int32_t rs_hip_isect_lds_budget( int32_t bytes );
 /* (diagnostics) Pairs the process rasterised since the last reset, and pairs rs_hip_nms settled without (cheap tests, disjoint boxes). */
 void    rs_hip_isect_pairs( int64_t* evaluated, int64_t* skipped, int32_t reset );
 
+/* ---- floor and wall planes: RANSAC votes, inlier gather, relabel ---- */
+
+/* rspf__detect_floor / rspf__detect_walls, rspf__gather_model_inliers and rspf_relabel_walls_and_floors
+ * (lib/rs/rs_pointcloud_filters.cpp:116-323, 617-671), bit for bit.  Everything is fp32 in the reference's association, compiled
+ * without contraction; msh_abs is x < 0 ? -x : x, so a NaN fails every compare.  Not covered, and why:
+ * rspf__split_by_connected_components and what needs its output (rspf__refine_plane_models, rspf_compute_plane_features,
+ * rspf_classify_planes).
+ *
+ * Refusals, all decided on the host with nothing written (rs_hip_last_error() says which):
+ *   RS_HIP_E_ARG       null arrays or negative counts; a round whose candidate set is empty (the reference's pdf would stay
+ *                      uninitialised); a wall round with fewer than 2 candidates (the reference's redraw loop never ends); a
+ *                      detection that would pop an empty model array (undefined in the reference)
+ *   RS_HIP_E_CAPACITY  n > 2^24 ((float)n is inexact in msh_rand_range); more models than the caller's capacity */
+
+/* One round's sampling on the host (no device needed): the alias table over weights 1.0 (active[i] != 0) / 0.0, the PCG32
+ * seeded with `seed` (the reference: 12346), n_iter triples idx[3h..3h+2] — distinct = 0 the floor's three plain samples,
+ * distinct = 1 the walls' redraws (b while b == a, c while c == b; c == a is allowed) — and per triple (each may be NULL)
+ * center = p_a and normal = normalize( cross( p_b - p_a, p_c - p_a ) ), NaN for a degenerate triple. */
+int rs_hip_plane_hypotheses( const float* pos, int64_t n, const uint8_t* active, int32_t n_iter, int32_t distinct, uint32_t seed,
+                             int32_t* idx, float* center, float* normal );
+
+/* evaluate_plane_model (:116-134) for n_hyp hypotheses at once, host arrays in and out: counts[h] = the number of points i with
+ * active[i] != 0 and msh_abs( dot( normal_h, pos_i - center_h ) ) < dist_threshold.  valid (may be NULL): a hypothesis with
+ * valid[h] == 0 is not scored (the walls' up test) and counts 0.  n = 0 or n_hyp = 0 succeed. */
+int rs_hip_plane_votes( const float* pos, int64_t n, const uint8_t* active, const float* center, const float* normal,
+                        const uint8_t* valid, int32_t n_hyp, float dist_threshold, int32_t* counts );
+
+/* What a detection did, round by round (round 0 is the floor's, rounds 1.. are the walls'), for tests and diagnostics.  The
+ * caller sets capacity_rounds, max_iters (>= both iteration counts) and the arrays, each of which may be NULL; round r's
+ * entries start at r * 3 * max_iters (idx), r * max_iters (valid, counts), r (best, n_iters) and r * n (mask_before,
+ * mask_after: the candidate mask the round sampled from, and the mask after its remove_inliers; the floor removes nothing).
+ * counts of hypotheses that failed the up test are 0; best is -1 where the round detected nothing.  Rounds beyond
+ * capacity_rounds are counted in n_rounds and not recorded. */
+typedef struct rs_hip_plane_trace
+{
+  int32_t capacity_rounds, max_iters;
+  int32_t n_rounds;
+  int32_t* idx; uint8_t* valid; int32_t* counts; int32_t* best; int32_t* n_iters;
+  uint8_t* mask_before; uint8_t* mask_after;
+} rs_hip_plane_trace_t;
+
+/* rspf__detect_floor then rspf__detect_walls on a cloud with normals (the reference: level 2 with ( 0.8f, 0.033f, 250, 2500,
+ * 5000 )).  The points stay on the device; per round the candidate mask comes to the host, the triples go back, and the best
+ * hypothesis' index and count come back.  Models in the reference's order (the floor first if one was found), n_inliers = the
+ * votes of each; *n_floors and *n_walls are the two functions' return values, *n_models the length of the array they leave.
+ * Kept as the reference has it: a wall round that detects nothing pushes nothing, removes the inliers of the previous best
+ * model (before any wall: the zero plane, which removes every candidate), ends the loop, and the final pop then removes a
+ * model that was legitimate — the previous wall or the floor. */
+int rs_hip_detect_planes( const rs_hip_cloud_t* cloud, float dot_threshold, float dist_threshold, int64_t count_threshold,
+                          int32_t floor_iters, int32_t wall_iters, int32_t capacity,
+                          float* centers /* 3 * capacity */, float* normals /* 3 * capacity */, int64_t* n_inliers /* capacity */,
+                          int32_t* n_floors, int32_t* n_walls, int32_t* n_models, rs_hip_plane_trace_t* trace /* may be NULL */ );
+
+/* A plane model crosses as plain arrays, model m at: centers[3m], normals[3m], axes[9m] (column-major: axes[9m + 3c + r]),
+ * extends[4m] (x, y, z, w), valid[m], normal_up_dot[m].  Arrays a call does not read may be NULL. */
+
+/* rspf__gather_model_inliers (:277-323) on a cloud with normals: for each model in order (skipped, with an empty range, if
+ * check_validity and valid[m] == 0) the indices i, increasing, with msh_abs( dot( nrm_i, n ) ) > dot_threshold and
+ * msh_abs( dot( n, p_i - c ) ) < dist_threshold and, with check_extends, rspf__is_point_within_convex_poly of the model's quad
+ * as written there (three of the four corners).  index[offsets[m] .. offsets[m + 1]) are model m's; offsets has n_models + 1
+ * entries.  More than `capacity` indices: RS_HIP_E_CAPACITY, nothing written. */
+int rs_hip_gather_plane_inliers( const rs_hip_cloud_t* cloud, const float* centers, const float* normals, const float* axes,
+                                 const float* extends, const int8_t* valid, int32_t n_models, float dot_threshold,
+                                 float dist_threshold, int32_t check_validity, int32_t check_extends,
+                                 int32_t* index, int64_t capacity, int64_t* offsets );
+
+/* rspf_relabel_walls_and_floors (:617-671) on a cloud with normals (the reference: level 1): the gather with dist_threshold
+ * 0.05f, dot_threshold 0 (the reference's params struct is zero-initialised and the function never sets it), validity and
+ * extends checked, and for every valid model in order and each of its inliers: normal_up_dot > 0.8f — instance >= 1024 -> 0,
+ * class == unlabelled_idx -> floor_idx; else instance >= 1024 -> 1, class == unlabelled_idx -> wall_idx.  class_ids and
+ * instance_ids (host, one entry per point of the cloud in the order it was created from) are rewritten in place. */
+int rs_hip_relabel_walls_and_floors( const rs_hip_cloud_t* cloud, const float* centers, const float* normals, const float* axes,
+                                     const float* extends, const int8_t* valid, const float* normal_up_dot, int32_t n_models,
+                                     int32_t floor_idx, int32_t wall_idx, int32_t unlabelled_idx,
+                                     int32_t* class_ids, int32_t* instance_ids );
+/* (measurements) 0: the votes kernel stages each tile of points in LDS (the default); 1: it reads them through wave-uniform global
+ * loads.  Same counts.  form < 0 only reads.  Returns the previous form. */
+int32_t rs_hip_plane_votes_form( int32_t form );
+
 /* ---- host-side helpers shared by the drop-in shim (exact reference arithmetic) ------- */
 
 /* msh_mat4_inverse / msh_mat4_mul (lib/msh/msh_vec_math.h:1818-1905, 1441-1476) */

@@ -112,6 +112,13 @@ SIGNATURES = {
     "rs_hip_cloud_create_fused": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                                C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "rs_hip_fuse_seconds": (None, [C.c_void_p, C.c_int32]),
+    "rs_hip_plane_hypotheses": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_plane_votes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
+    "rs_hip_detect_planes": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]),
+    "rs_hip_gather_plane_inliers": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "rs_hip_relabel_walls_and_floors": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
+    "rs_hip_plane_votes_form": (C.c_int32, [C.c_int32]),
     "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rs_hip_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
@@ -306,6 +313,11 @@ class Cloud:
         _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, self._nor.ctypes.data))
         return self, info
 
+    def detect_planes(self, dot_threshold=0.8, dist_threshold=0.033, count_threshold=250, floor_iters=2500, wall_iters=5000, capacity=64,
+                      trace=False):
+        """rspf__detect_floor then rspf__detect_walls on this cloud (the reference: level 2), see detect_planes()."""
+        return detect_planes(self, dot_threshold, dist_threshold, count_threshold, floor_iters, wall_iters, capacity, trace)
+
     @property
     def nbytes(self):
         return load().rs_hip_cloud_bytes(self.handle)
@@ -418,6 +430,110 @@ def fuse_seconds(enable=True):
 
 
 KNN_MAX_K = 64          # RS_HIP_KNN_MAX_K
+
+
+SEED_PLANES = 12346     # rspf__detect_floor / rspf__detect_walls (lib/rs/rs_pointcloud_filters.cpp:154,217)
+
+
+class PlaneTrace(C.Structure):
+    """rs_hip_plane_trace_t"""
+    _fields_ = [("capacity_rounds", C.c_int32), ("max_iters", C.c_int32), ("n_rounds", C.c_int32), ("idx", C.c_void_p), ("valid", C.c_void_p),
+                ("counts", C.c_void_p), ("best", C.c_void_p), ("n_iters", C.c_void_p), ("mask_before", C.c_void_p), ("mask_after", C.c_void_p)]
+
+
+def plane_hypotheses(pos, active, n_iter, distinct, seed=SEED_PLANES):
+    """One RANSAC round's sampling on the host (rs_hip_plane_hypotheses; no device needed): (idx (n_iter, 3), center, normal)."""
+    pos = _f32(pos).reshape(-1, 3); active = np.ascontiguousarray(active, np.uint8).ravel()
+    if len(active) != len(pos):
+        raise ValueError("active: one entry per point")
+    idx = np.zeros((n_iter, 3), np.int32); center = np.zeros((n_iter, 3), np.float32); normal = np.zeros((n_iter, 3), np.float32)
+    _check(load().rs_hip_plane_hypotheses(pos.ctypes.data, len(pos), active.ctypes.data, int(n_iter), int(bool(distinct)), int(seed),
+                                          idx.ctypes.data, center.ctypes.data, normal.ctypes.data))
+    return idx, center, normal
+
+
+def plane_votes(pos, active, center, normal, dist_threshold, valid=None):
+    """evaluate_plane_model for every hypothesis at once (rs_hip_plane_votes): int32 counts, 0 where valid[h] == 0."""
+    pos = _f32(pos).reshape(-1, 3); active = np.ascontiguousarray(active, np.uint8).ravel()
+    center = _f32(center).reshape(-1, 3); normal = _f32(normal).reshape(-1, 3)
+    if len(active) != len(pos) or len(center) != len(normal):
+        raise ValueError("active: one entry per point; center and normal: one row per hypothesis")
+    valid = None if valid is None else np.ascontiguousarray(valid, np.uint8).ravel()
+    counts = np.zeros(len(center), np.int32)
+    _check(load().rs_hip_plane_votes(pos.ctypes.data, len(pos), active.ctypes.data, center.ctypes.data, normal.ctypes.data,
+                                     None if valid is None else valid.ctypes.data, len(center), float(dist_threshold), counts.ctypes.data))
+    return counts
+
+
+def plane_votes_form(form=-1):
+    """rs_hip_plane_votes_form: 0 the LDS tile (default), 1 wave-uniform global loads; < 0 only reads.  Returns the previous form."""
+    return load().rs_hip_plane_votes_form(int(form))
+
+
+def detect_planes(cloud, dot_threshold=0.8, dist_threshold=0.033, count_threshold=250, floor_iters=2500, wall_iters=5000, capacity=64,
+                  trace=False, trace_rounds=32):
+    """rs_hip_detect_planes: dict(centers, normals, n_inliers, n_floors, n_walls) and, with trace, trace = dict(n_rounds, idx, valid,
+    counts, best, n_iters, mask_before, mask_after), one leading entry per recorded round (round 0: the floor)."""
+    centers = np.zeros((capacity, 3), np.float32); normals = np.zeros((capacity, 3), np.float32); n_inl = np.zeros(capacity, np.int64)
+    nf, nw, nm = C.c_int32(), C.c_int32(), C.c_int32()
+    t = None
+    if trace:
+        mi = max(int(floor_iters), int(wall_iters), 1); r = int(trace_rounds)
+        arrays = dict(idx=np.zeros((r, mi, 3), np.int32), valid=np.zeros((r, mi), np.uint8), counts=np.zeros((r, mi), np.int32),
+                      best=np.full(r, -2, np.int32), n_iters=np.zeros(r, np.int32), mask_before=np.zeros((r, cloud.n), np.uint8),
+                      mask_after=np.zeros((r, cloud.n), np.uint8))
+        t = PlaneTrace(r, mi, 0, *[arrays[k].ctypes.data for k in ("idx", "valid", "counts", "best", "n_iters", "mask_before", "mask_after")])
+    _check(load().rs_hip_detect_planes(cloud.handle, float(dot_threshold), float(dist_threshold), int(count_threshold), int(floor_iters),
+                                       int(wall_iters), int(capacity), centers.ctypes.data, normals.ctypes.data, n_inl.ctypes.data,
+                                       C.byref(nf), C.byref(nw), C.byref(nm), C.addressof(t) if t is not None else None))
+    m = nm.value
+    out = dict(centers=centers[:m].copy(), normals=normals[:m].copy(), n_inliers=n_inl[:m].copy(), n_floors=nf.value, n_walls=nw.value)
+    if trace:
+        k = min(t.n_rounds, r)
+        out["trace"] = dict(n_rounds=t.n_rounds, **{key: a[:k] for key, a in arrays.items()})
+    return out
+
+
+def _plane_models(centers, normals, axes=None, extends=None, valid=None, normal_up_dot=None):
+    centers = _f32(centers).reshape(-1, 3); m = len(centers)
+    normals = _f32(normals).reshape(-1, 3)
+    axes = None if axes is None else _f32(axes).reshape(-1, 9)
+    extends = None if extends is None else _f32(extends).reshape(-1, 4)
+    valid = None if valid is None else np.ascontiguousarray(valid, np.int8).ravel()
+    up = None if normal_up_dot is None else _f32(normal_up_dot).ravel()
+    for a in (normals, axes, extends, valid, up):
+        if a is not None and len(a) != m:
+            raise ValueError("plane models: every array has one row per model")
+    return m, [None if a is None else a.ctypes.data for a in (centers, normals, axes, extends, valid, up)], (centers, normals, axes, extends, valid, up)
+
+
+def gather_plane_inliers(cloud, centers, normals, axes=None, extends=None, valid=None, dot_threshold=0.8, dist_threshold=0.05,
+                         check_validity=False, check_extends=False):
+    """rspf__gather_model_inliers (rs_hip_gather_plane_inliers): a list with one increasing int32 index array per model.  axes: (M, 9)
+    column-major, extends (M, 4), valid (M,)."""
+    m, ptrs, keep = _plane_models(centers, normals, axes, extends, valid)
+    lib = load()
+    offsets = np.zeros(m + 1, np.int64)
+    capacity = max(cloud.n, 1)
+    while True:
+        index = np.zeros(capacity, np.int32)
+        rc = lib.rs_hip_gather_plane_inliers(cloud.handle, *ptrs[:5], m, float(dot_threshold), float(dist_threshold), int(bool(check_validity)),
+                                             int(bool(check_extends)), index.ctypes.data, capacity, offsets.ctypes.data)
+        if rc == -4 and capacity < m * max(cloud.n, 1) and b"capacity" in lib.rs_hip_last_error():
+            capacity = m * max(cloud.n, 1)
+            continue
+        _check(rc)
+        return [index[offsets[k]:offsets[k + 1]].copy() for k in range(m)]
+
+
+def relabel_walls_and_floors(cloud, centers, normals, axes, extends, valid, normal_up_dot, floor_idx, wall_idx, unlabelled_idx, class_ids, instance_ids):
+    """rspf_relabel_walls_and_floors on a level-1 cloud (rs_hip_relabel_walls_and_floors): the rewritten (class_ids, instance_ids)."""
+    m, ptrs, keep = _plane_models(centers, normals, axes, extends, valid, normal_up_dot)
+    cls = np.array(class_ids, np.int32).ravel(); inst = np.array(instance_ids, np.int32).ravel()
+    if len(cls) != cloud.n or len(inst) != cloud.n:
+        raise ValueError("class_ids, instance_ids: one entry per point")
+    _check(load().rs_hip_relabel_walls_and_floors(cloud.handle, *ptrs, m, int(floor_idx), int(wall_idx), int(unlabelled_idx), cls.ctypes.data, inst.ctypes.data))
+    return cls, inst
 
 
 class KnnGrid:

@@ -931,6 +931,54 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
   return (int64_t)n;
 }
 
+int32_t rsd_detect_floor_and_walls( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, float dot_threshold, float dist_threshold,
+                                    int64_t count_threshold, int32_t capacity, rsd_vec3_t* centers, rsd_vec3_t* normals, int64_t* n_inliers,
+                                    int32_t* n_floors, int32_t* n_walls )
+{
+  if( !pos || !nor || n <= 0 || n > 2147483647ll || !n_floors || !n_walls )
+  { fprintf( stderr, "rescan_dropin: detect_floor_and_walls: null arrays or no points\n" ); return RS_HIP_E_ARG; }
+  const CloudRef c = cached_cloud( pos, nor, (int32_t)n, -1.0f );
+  if( !c ) return RS_HIP_E_RUNTIME;
+  int32_t n_models = 0;
+  const int rc = rs_hip_detect_planes( c.get(), dot_threshold, dist_threshold, count_threshold, 2500, 5000, capacity, (float*)centers, (float*)normals,
+                                       n_inliers, n_floors, n_walls, &n_models, nullptr );         // rs_pointcloud_filters.cpp:149,219
+  if( rc ) { complain( "detect_floor_and_walls" ); return rc; }
+  return n_models;
+}
+
+int64_t rsd_gather_model_inliers( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, const rsd_vec3_t* centers, const rsd_vec3_t* normals,
+                                  const float* axes, const float* extends, const int8_t* valid, int32_t n_models, float dot_threshold,
+                                  float dist_threshold, int32_t check_validity, int32_t check_extends, int32_t** index, int64_t* offsets )
+{
+  if( !pos || !nor || n <= 0 || n > 2147483647ll || n_models < 0 || !index || !offsets )
+  { fprintf( stderr, "rescan_dropin: gather_model_inliers: null arrays or no points\n" ); return RS_HIP_E_ARG; }
+  *index = nullptr;
+  const CloudRef c = cached_cloud( pos, nor, (int32_t)n, -1.0f );
+  if( !c ) return RS_HIP_E_RUNTIME;
+  const size_t cap = (size_t)n * (size_t)( n_models > 0 ? n_models : 1 );
+  int32_t* out = (int32_t*)malloc( cap * sizeof(int32_t) );
+  if( !out ) return RS_HIP_E_RUNTIME;
+  const int rc = rs_hip_gather_plane_inliers( c.get(), (const float*)centers, (const float*)normals, axes, extends, valid, n_models, dot_threshold,
+                                              dist_threshold, check_validity, check_extends, out, (int64_t)cap, offsets );
+  if( rc ) { free( out ); complain( "gather_model_inliers" ); return rc; }
+  *index = out;
+  return offsets[n_models];
+}
+
+int rsd_relabel_walls_and_floors( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, const rsd_vec3_t* centers, const rsd_vec3_t* normals,
+                                  const float* axes, const float* extends, const int8_t* valid, const float* normal_up_dot, int32_t n_models,
+                                  int32_t floor_idx, int32_t wall_idx, int32_t unlabelled_idx, int32_t* class_ids, int32_t* instance_ids )
+{
+  if( !pos || !nor || n <= 0 || n > 2147483647ll )
+  { fprintf( stderr, "rescan_dropin: relabel_walls_and_floors: null arrays or no points\n" ); return RS_HIP_E_ARG; }
+  const CloudRef c = cached_cloud( pos, nor, (int32_t)n, -1.0f );
+  if( !c ) return RS_HIP_E_RUNTIME;
+  const int rc = rs_hip_relabel_walls_and_floors( c.get(), (const float*)centers, (const float*)normals, axes, extends, valid, normal_up_dot, n_models,
+                                                  floor_idx, wall_idx, unlabelled_idx, class_ids, instance_ids );
+  if( rc ) complain( "relabel_walls_and_floors" );
+  return rc;
+}
+
 void* rsd_coverage_create( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
                            const rsd_vec3_t* scene_pos, const float* scene_quality, int32_t n_scene, float quality_threshold )
 {

@@ -85,9 +85,35 @@ inline uint64_t jump( const JumpTable& t, int which, uint64_t steps )
 
 // ---- areas, sample count, alias table ------------------------------------------------------------------------------
 
+// The alias table of msh_discrete_distribution_update (msh_std.h:1871-1910) over a pdf of n entries, which it consumes.  An alias
+// entry the reference never writes (prob = 1.0 leftovers, :1899-1910; malloc'ed and unread there) holds its own index.  Shared
+// by the resampler's plan below and the plane detector's sampler (rs_planes.h).
+inline void alias_table( double* pdf, size_t n, double* prob, int32_t* alias )
+{
+  const double avg = 1.0 / (double)n;
+  // The two stacks together never hold more than n entries (every entry starts on one; a round pops two and pushes one),
+  // so n slots each are enough.
+  std::vector<int32_t> small( n ), large( n );
+  size_t n_small = 0, n_large = 0;
+  for( size_t i = 0; i < n; ++i )
+  {
+    alias[i] = (int32_t)i;
+    if( pdf[i] >= avg ) large[n_large++] = (int32_t)i; else small[n_small++] = (int32_t)i;
+  }
+  while( n_small && n_large )
+  {
+    const int32_t l = small[--n_small], g = large[--n_large];
+    prob[l] = pdf[l] * (double)n;
+    alias[l] = g;
+    pdf[g] = ( pdf[g] + pdf[l] ) - avg;
+    if( pdf[g] >= avg ) large[n_large++] = g; else small[n_small++] = g;
+  }
+  while( n_small ) prob[small[--n_small]] = 1.0;
+  while( n_large ) prob[large[--n_large]] = 1.0;
+}
+
 // n_samples, total_area and (where asked for: prob and alias may each be null) the alias table of the
-// reference's call.  Returns RS_HIP_OK or the refusal's code with its text in err.  An alias entry the reference never
-// writes (prob = 1.0 leftovers, msh_std.h:1899-1910; malloc'ed and unread there) holds its own index here.
+// reference's call.  Returns RS_HIP_OK or the refusal's code with its text in err.
 inline int plan( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
                  int64_t* n_samples, double* total_area, double* prob, int32_t* alias, char* err, size_t err_cap )
 {
@@ -132,26 +158,7 @@ inline int plan( const float* pos, int64_t n_vertices, const int32_t* faces, int
   if( !alias ) { alias_own.resize( n ); alias = alias_own.data(); }
   const double inv_sum = 1.0 / sum;
   for( size_t i = 0; i < n; ++i ) pdf[i] = areas[i] * inv_sum;
-  const double avg = 1.0 / (double)n;
-  // The two stacks together never hold more than n entries (every face starts on one; a round pops two and pushes one),
-  // so n slots each are enough.
-  std::vector<int32_t> small( n ), large( n );
-  size_t n_small = 0, n_large = 0;
-  for( size_t i = 0; i < n; ++i )
-  {
-    alias[i] = (int32_t)i;
-    if( pdf[i] >= avg ) large[n_large++] = (int32_t)i; else small[n_small++] = (int32_t)i;
-  }
-  while( n_small && n_large )
-  {
-    const int32_t l = small[--n_small], g = large[--n_large];
-    prob[l] = pdf[l] * (double)n;
-    alias[l] = g;
-    pdf[g] = ( pdf[g] + pdf[l] ) - avg;
-    if( pdf[g] >= avg ) large[n_large++] = g; else small[n_small++] = g;
-  }
-  while( n_small ) prob[small[--n_small]] = 1.0;
-  while( n_large ) prob[large[--n_large]] = 1.0;
+  alias_table( pdf.data(), n, prob, alias );
   return RS_HIP_OK;
 #undef RS_MESH_REFUSE
 }
