@@ -8,6 +8,7 @@
 
 #include "../../include/rescan_hip.h"
 #include "rs_device.h"
+#include "rs_host.h"
 #include "rs_math.h"
 #include "rs_voxel.h"
 
@@ -2699,7 +2700,7 @@ extern "C" int rs_hip_coverage_scores( rs_hip_coverage_t* c, const rs_hip_cloud_
 }
 
 // ------------------------------------------------------------------------------------------
-// what the translation units with entry points of their own (rs_knn.hip, rs_isect.hip) need from this one
+// what the translation units with entry points of their own need from this one (declared in rs_host.h)
 // ------------------------------------------------------------------------------------------
 
 namespace rs {

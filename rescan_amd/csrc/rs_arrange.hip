@@ -25,7 +25,7 @@
 // (rs_isect.hip takes the boxes in a launch of their own and routes on the host before the main launch.  Here the box needs the
 //  two planes, not the pose alone, and the common case is "every candidate fits": deciding inside the workgroup saves that launch
 //  and its read-back for all of them.)
-#include "../../include/rescan_hip.h"
+#include "rs_host.h"
 #include "rs_search.h"
 #include "rs_voxel.h"
 
@@ -165,37 +165,16 @@ __global__ __launch_bounds__( ARR_BLOCK ) void k_extend( ExtLaunch L )
 
 // ------------------------------------------------------------------------------------------
 
-struct ArrBuf
-{
-  void* p = nullptr; size_t cap = 0; bool pinned = false;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = pinned ? hipHostFree( p ) : hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = pinned ? hipHostMalloc( &p, want, hipHostMallocDefault ) : hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-  hipError_t release()
-  {
-    if( !p ) return hipSuccess;
-    const hipError_t e = pinned ? hipHostFree( p ) : hipFree( p );
-    p = nullptr; cap = 0;
-    return e;
-  }
-};
 // The calling thread's buffers, grown on demand and kept between calls (a base plane, the placements, and a slab of up to
-// ARR_SLAB_BYTES once a call took the global route).  They have NO destructor on purpose: a thread_local's destructor of the main
-// thread runs at process exit, where the HIP runtime may already be gone, and freeing into it is worse than leaving the memory to
-// the process.  A thread that ends while the process goes on gives them back with rs_hip_arrange_release().
+// ARR_SLAB_BYTES once a call took the global route).  No destructor frees them (rs_host.h: Buf); a thread that ends while the
+// process goes on gives them back with rs_hip_arrange_release().
 struct ArrWorkspace
 {
-  ArrBuf props, bits, pos, cls, quality, base, plc, out, over, jobs, slab, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true };
+  Buf props, bits, pos, cls, quality, base, plc, out, over, jobs, slab, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true };
   hipError_t release()
   {
     hipError_t first = hipSuccess;
-    for( ArrBuf* b : { &props, &bits, &pos, &cls, &quality, &base, &plc, &out, &over, &jobs, &slab, &h_in, &h_out } )
+    for( Buf* b : { &props, &bits, &pos, &cls, &quality, &base, &plc, &out, &over, &jobs, &slab, &h_in, &h_out } )
     {
       const hipError_t e = b->release();
       if( first == hipSuccess ) first = e;
@@ -207,19 +186,6 @@ thread_local ArrWorkspace g_arr_ws;
 // process-wide, read and written by any calling thread
 std::atomic<int> g_arr_lds_bytes{ ARR_LDS_BYTES };
 std::atomic<int64_t> g_arr_lds_route{ 0 }, g_arr_slab_route{ 0 };
-
-int fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-// (a failed step leaves the call at once, but not before the stream has drained: copies to or from the pinned buffers and the
-//  caller's arrays may be in flight, and the next call reuses or frees them)
-// NOT between api_prof_begin and api_prof_end: the early return would leave the profiling span open.  Launches inside a span are
-// checked by the hipGetLastError that follows api_prof_end.
-#define ARR_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) { (void)hipStreamSynchronize( st ); return fail( RS_HIP_E_RUNTIME, what, e_ ); } } while( 0 )
 
 } // namespace
 
@@ -271,41 +237,42 @@ int rs_hip_scene_saliency( const float bbox_min[3], const float bbox_max[3], flo
       if( phase == 0 ) ++n_dyn;
     }
   const size_t n_words = ( (size_t)g.n_cells + 31 ) / 32;
-  ARR_TRY( W.bits.ensure( n_words * 4 ), "scene_saliency: buffers" );
-  ARR_TRY( hipMemsetAsync( W.bits.p, 0, n_words * 4, st ), "scene_saliency: clear" );              // isect_grid3d_init's memset (intersect.h:74)
+  RS_TRY_DRAIN( st, W.bits.ensure( n_words * 4 ), "scene_saliency: buffers" );
+  RS_TRY_DRAIN( st, hipMemsetAsync( W.bits.p, 0, n_words * 4, st ), "scene_saliency: clear" );              // isect_grid3d_init's memset (intersect.h:74)
   if( !props.empty() )
   {
-    ARR_TRY( W.props.ensure( props.size() * sizeof(ArrProposal) ), "scene_saliency: buffers" );
-    ARR_TRY( W.h_in.ensure( props.size() * sizeof(ArrProposal) ), "scene_saliency: buffers" );
+    RS_TRY_DRAIN( st, W.props.ensure( props.size() * sizeof(ArrProposal) ), "scene_saliency: buffers" );
+    RS_TRY_DRAIN( st, W.h_in.ensure( props.size() * sizeof(ArrProposal) ), "scene_saliency: buffers" );
     std::memcpy( W.h_in.p, props.data(), props.size() * sizeof(ArrProposal) );
-    ARR_TRY( hipMemcpyAsync( W.props.p, W.h_in.p, props.size() * sizeof(ArrProposal), hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.props.p, W.h_in.p, props.size() * sizeof(ArrProposal), hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
   }
   if( n_scene > 0 )
   {
-    ARR_TRY( W.pos.ensure( (size_t)n_scene * 12 ), "scene_saliency: buffers" );
-    ARR_TRY( W.cls.ensure( (size_t)n_scene * 4 ), "scene_saliency: buffers" );
-    ARR_TRY( W.quality.ensure( (size_t)n_scene * 4 ), "scene_saliency: buffers" );
-    ARR_TRY( hipMemcpyAsync( W.pos.p, scene_pos, (size_t)n_scene * 12, hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
-    ARR_TRY( hipMemcpyAsync( W.cls.p, scene_class, (size_t)n_scene * 4, hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
+    RS_TRY_DRAIN( st, W.pos.ensure( (size_t)n_scene * 12 ), "scene_saliency: buffers" );
+    RS_TRY_DRAIN( st, W.cls.ensure( (size_t)n_scene * 4 ), "scene_saliency: buffers" );
+    RS_TRY_DRAIN( st, W.quality.ensure( (size_t)n_scene * 4 ), "scene_saliency: buffers" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.pos.p, scene_pos, (size_t)n_scene * 12, hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.cls.p, scene_class, (size_t)n_scene * 4, hipMemcpyHostToDevice, st ), "scene_saliency: upload" );
   }
-  void* ev = api_prof_begin();
-  const int n_phase[2] = { n_dyn, (int)props.size() - n_dyn };
-  for( int phase = 0; phase < 2; ++phase )
   {
-    const int bx = std::max( 1, std::min( 64, ( max_pts[phase] + ARR_BLOCK - 1 ) / ARR_BLOCK ) );
-    for( int first = 0; first < n_phase[phase]; first += ARR_MAX_GRID_Y )          // (any number of proposals: launches of at most 65535)
-      hipLaunchKernelGGL( k_saliency_raster, dim3( bx, std::min( ARR_MAX_GRID_Y, n_phase[phase] - first ) ), dim3( ARR_BLOCK ), 0, st, g,
-                          (const ArrProposal*)W.props.p + ( phase ? n_dyn : 0 ) + first, phase == 0 ? 1 : 0, (uint32_t*)W.bits.p );
+    ProfSpan span( "saliency" );
+    const int n_phase[2] = { n_dyn, (int)props.size() - n_dyn };
+    for( int phase = 0; phase < 2; ++phase )
+    {
+      const int bx = std::max( 1, std::min( 64, ( max_pts[phase] + ARR_BLOCK - 1 ) / ARR_BLOCK ) );
+      for( int first = 0; first < n_phase[phase]; first += ARR_MAX_GRID_Y )          // (any number of proposals: launches of at most 65535)
+        hipLaunchKernelGGL( k_saliency_raster, dim3( bx, std::min( ARR_MAX_GRID_Y, n_phase[phase] - first ) ), dim3( ARR_BLOCK ), 0, st, g,
+                            (const ArrProposal*)W.props.p + ( phase ? n_dyn : 0 ) + first, phase == 0 ? 1 : 0, (uint32_t*)W.bits.p );
+    }
+    if( n_scene > 0 )
+      hipLaunchKernelGGL( k_saliency_lookup, dim3( blocks_for( n_scene, ARR_BLOCK ) ), dim3( ARR_BLOCK ), 0, st, g,
+                          (const float*)W.pos.p, (const int*)W.cls.p, (long long)n_scene, (int)wall_class, (int)floor_class, (const uint32_t*)W.bits.p, (float*)W.quality.p );
   }
-  if( n_scene > 0 )
-    hipLaunchKernelGGL( k_saliency_lookup, dim3( (unsigned)( ( n_scene + ARR_BLOCK - 1 ) / ARR_BLOCK ) ), dim3( ARR_BLOCK ), 0, st, g,
-                        (const float*)W.pos.p, (const int*)W.cls.p, (long long)n_scene, (int)wall_class, (int)floor_class, (const uint32_t*)W.bits.p, (float*)W.quality.p );
-  api_prof_end( "saliency", ev );
-  ARR_TRY( hipGetLastError(), "scene_saliency: launch" );
-  if( n_scene > 0 ) ARR_TRY( hipMemcpyAsync( quality, W.quality.p, (size_t)n_scene * 4, hipMemcpyDeviceToHost, st ), "scene_saliency: download" );
+  RS_TRY_DRAIN( st, hipGetLastError(), "scene_saliency: launch" );
+  if( n_scene > 0 ) RS_TRY_DRAIN( st, hipMemcpyAsync( quality, W.quality.p, (size_t)n_scene * 4, hipMemcpyDeviceToHost, st ), "scene_saliency: download" );
   std::vector<uint32_t> hb;
-  if( grid ) { hb.resize( n_words ); ARR_TRY( hipMemcpyAsync( hb.data(), W.bits.p, n_words * 4, hipMemcpyDeviceToHost, st ), "scene_saliency: download" ); }
-  ARR_TRY( hipStreamSynchronize( st ), "scene_saliency" );       // (also keeps the caller's arrays and `hb` in use until the copies are done)
+  if( grid ) { hb.resize( n_words ); RS_TRY_DRAIN( st, hipMemcpyAsync( hb.data(), W.bits.p, n_words * 4, hipMemcpyDeviceToHost, st ), "scene_saliency: download" ); }
+  RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "scene_saliency" );       // (also keeps the caller's arrays and `hb` in use until the copies are done)
   if( grid ) for( int i = 0; i < g.n_cells; ++i ) grid[i] = ( hb[(size_t)i >> 5] >> ( i & 31 ) ) & 1u;      // 1 = RSAO_CELL_ACTIVE
   return RS_HIP_OK;
 }
@@ -353,45 +320,46 @@ int rs_hip_coverage_extensions( rs_hip_coverage_t* c,
   }
   // device words of a call: [0] agree( base ), [1] candidates on the overflow list, [2 ..) fresh per candidate
   const size_t out_ints = 2 + (size_t)n_cand, plane_bytes = (size_t)c->n_words * 4;
-  ARR_TRY( W.base.ensure( plane_bytes ), "coverage_extensions: buffers" );
-  ARR_TRY( W.out.ensure( out_ints * 4 ), "coverage_extensions: buffers" );
-  ARR_TRY( W.over.ensure( std::max<size_t>( 1, n_cand ) * sizeof(ArrOverflow) ), "coverage_extensions: buffers" );
-  ARR_TRY( W.plc.ensure( std::max<size_t>( 1, plc.size() ) * sizeof(CoveragePlacement) ), "coverage_extensions: buffers" );
-  ARR_TRY( W.h_in.ensure( std::max<size_t>( 1, plc.size() ) * sizeof(CoveragePlacement) ), "coverage_extensions: buffers" );
-  ARR_TRY( W.h_out.ensure( out_ints * 4 + 8 + std::max<size_t>( 1, n_cand ) * sizeof(ArrOverflow) ), "coverage_extensions: buffers" );
-  ARR_TRY( hipMemsetAsync( W.base.p, 0, plane_bytes, st ), "coverage_extensions: clear" );          // ONE plane per call (:1089)
-  ARR_TRY( hipMemsetAsync( W.out.p, 0, 8, st ), "coverage_extensions: clear" );
+  RS_TRY_DRAIN( st, W.base.ensure( plane_bytes ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, W.out.ensure( out_ints * 4 ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, W.over.ensure( std::max<size_t>( 1, n_cand ) * sizeof(ArrOverflow) ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, W.plc.ensure( std::max<size_t>( 1, plc.size() ) * sizeof(CoveragePlacement) ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, W.h_in.ensure( std::max<size_t>( 1, plc.size() ) * sizeof(CoveragePlacement) ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, W.h_out.ensure( out_ints * 4 + 8 + std::max<size_t>( 1, n_cand ) * sizeof(ArrOverflow) ), "coverage_extensions: buffers" );
+  RS_TRY_DRAIN( st, hipMemsetAsync( W.base.p, 0, plane_bytes, st ), "coverage_extensions: clear" );          // ONE plane per call (:1089)
+  RS_TRY_DRAIN( st, hipMemsetAsync( W.out.p, 0, 8, st ), "coverage_extensions: clear" );
   if( !plc.empty() )
   {
     std::memcpy( W.h_in.p, plc.data(), plc.size() * sizeof(CoveragePlacement) );
-    ARR_TRY( hipMemcpyAsync( W.plc.p, W.h_in.p, plc.size() * sizeof(CoveragePlacement), hipMemcpyHostToDevice, st ), "coverage_extensions: upload" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.plc.p, W.h_in.p, plc.size() * sizeof(CoveragePlacement), hipMemcpyHostToDevice, st ), "coverage_extensions: upload" );
   }
   int* d_out = (int*)W.out.p;
-  void* ev = api_prof_begin();
-  if( n_base_plc )
-  {
-    CoverageLaunch B{};
-    B.grid = c->grid; B.scene_bits = c->d_bits; B.arr_bits = (uint32_t*)W.base.p; B.n_words = c->n_words;
-    B.plc = (const CoveragePlacement*)W.plc.p; B.n_plc = (int)n_base_plc; B.max_pts = base_max; B.agree = d_out;
-    launch_coverage( B, st );
-  }
   ExtLaunch L{};
   L.grid = c->grid; L.scene_bits = c->d_bits; L.base_bits = (const uint32_t*)W.base.p;
   L.cand = (const CoveragePlacement*)W.plc.p + n_base_plc; L.lds_bytes = g_arr_lds_bytes.load();
   L.fresh = d_out + 2; L.n_overflow = d_out + 1; L.overflow = (ArrOverflow*)W.over.p;
-  if( n_cand > 0 ) hipLaunchKernelGGL( k_extend<false>, dim3( (unsigned)n_cand ), dim3( ARR_BLOCK ), 0, st, L );
-  api_prof_end( "coverage", ev );
-  ARR_TRY( hipGetLastError(), "coverage_extensions: launch" );
+  {
+    ProfSpan span( "coverage" );
+    if( n_base_plc )
+    {
+      CoverageLaunch B{};
+      B.grid = c->grid; B.scene_bits = c->d_bits; B.arr_bits = (uint32_t*)W.base.p; B.n_words = c->n_words;
+      B.plc = (const CoveragePlacement*)W.plc.p; B.n_plc = (int)n_base_plc; B.max_pts = base_max; B.agree = d_out;
+      launch_coverage( B, st );
+    }
+    if( n_cand > 0 ) hipLaunchKernelGGL( k_extend<false>, dim3( (unsigned)n_cand ), dim3( ARR_BLOCK ), 0, st, L );
+  }
+  RS_TRY_DRAIN( st, hipGetLastError(), "coverage_extensions: launch" );
   int* h_out = (int*)W.h_out.p;
-  ARR_TRY( hipMemcpyAsync( h_out, d_out, out_ints * 4, hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
-  ARR_TRY( hipStreamSynchronize( st ), "coverage_extensions" );
+  RS_TRY_DRAIN( st, hipMemcpyAsync( h_out, d_out, out_ints * 4, hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
+  RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_extensions" );
   const int n_over = h_out[1];
   if( n_over < 0 || n_over > n_cand ) return fail( RS_HIP_E_RUNTIME, "coverage_extensions: overflow list out of range" );
   if( n_over > 0 )
   {
     ArrOverflow* ho = (ArrOverflow*)( h_out + out_ints + ( out_ints & 1 ) );
-    ARR_TRY( hipMemcpyAsync( ho, W.over.p, (size_t)n_over * sizeof(ArrOverflow), hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
-    ARR_TRY( hipStreamSynchronize( st ), "coverage_extensions" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( ho, W.over.p, (size_t)n_over * sizeof(ArrOverflow), hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
+    RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_extensions" );
     std::sort( ho, ho + n_over, []( const ArrOverflow& a, const ArrOverflow& b ) { return a.cand < b.cand; } );       // (the list's order is the workgroups')
     std::vector<ArrSlabJob> jobs( n_over );
     std::vector<std::pair<int, int>> chunks;                       // launches of at most ARR_SLAB_BYTES of sub-boxes
@@ -406,20 +374,21 @@ int rs_hip_coverage_extensions( rs_hip_coverage_t* c,
       }
       chunks.emplace_back( i, j ); slab_words = std::max( slab_words, used ); i = j;
     }
-    ARR_TRY( W.slab.ensure( slab_words * 4 ), "coverage_extensions: scratch slab" );
-    ARR_TRY( W.jobs.ensure( jobs.size() * sizeof(ArrSlabJob) ), "coverage_extensions: buffers" );
-    ARR_TRY( hipMemcpyAsync( W.jobs.p, jobs.data(), jobs.size() * sizeof(ArrSlabJob), hipMemcpyHostToDevice, st ), "coverage_extensions: upload" );
+    RS_TRY_DRAIN( st, W.slab.ensure( slab_words * 4 ), "coverage_extensions: scratch slab" );
+    RS_TRY_DRAIN( st, W.jobs.ensure( jobs.size() * sizeof(ArrSlabJob) ), "coverage_extensions: buffers" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.jobs.p, jobs.data(), jobs.size() * sizeof(ArrSlabJob), hipMemcpyHostToDevice, st ), "coverage_extensions: upload" );
     L.slab = (uint32_t*)W.slab.p;
-    ev = api_prof_begin();
-    for( const auto& ch : chunks )
     {
-      L.jobs = (const ArrSlabJob*)W.jobs.p + ch.first;
-      hipLaunchKernelGGL( k_extend<true>, dim3( (unsigned)( ch.second - ch.first ) ), dim3( ARR_BLOCK ), 0, st, L );
+      ProfSpan span( "coverage" );
+      for( const auto& ch : chunks )
+      {
+        L.jobs = (const ArrSlabJob*)W.jobs.p + ch.first;
+        hipLaunchKernelGGL( k_extend<true>, dim3( (unsigned)( ch.second - ch.first ) ), dim3( ARR_BLOCK ), 0, st, L );
+      }
     }
-    api_prof_end( "coverage", ev );
-    ARR_TRY( hipGetLastError(), "coverage_extensions: launch" );
-    ARR_TRY( hipMemcpyAsync( h_out, d_out, out_ints * 4, hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
-    ARR_TRY( hipStreamSynchronize( st ), "coverage_extensions" );      // (also keeps `jobs` alive until the upload is done)
+    RS_TRY_DRAIN( st, hipGetLastError(), "coverage_extensions: launch" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( h_out, d_out, out_ints * 4, hipMemcpyDeviceToHost, st ), "coverage_extensions: download" );
+    RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_extensions" );      // (also keeps `jobs` alive until the upload is done)
   }
   g_arr_lds_route += n_cand - n_over; g_arr_slab_route += n_over;
   const int base_cnt = h_out[0];
@@ -446,7 +415,7 @@ int rs_hip_arrange_release( void )
 {
   ArrWorkspace& W = g_arr_ws;
   bool any = false;
-  for( const ArrBuf* b : { &W.props, &W.bits, &W.pos, &W.cls, &W.quality, &W.base, &W.plc, &W.out, &W.over, &W.jobs, &W.slab, &W.h_in, &W.h_out } ) any = any || b->p;
+  for( const Buf* b : { &W.props, &W.bits, &W.pos, &W.cls, &W.quality, &W.base, &W.plc, &W.out, &W.over, &W.jobs, &W.slab, &W.h_in, &W.h_out } ) any = any || b->p;
   if( !any ) return RS_HIP_OK;                                   // (nothing held: no device is touched)
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;

@@ -367,19 +367,4 @@ void launch_edge_count( const EdgeLaunch& L, hipStream_t st );   // fills count
 void launch_edge_scan( const EdgeLaunch& L, hipStream_t st );    // count -> offset (single workgroup, fixed order)
 void launch_edge_write( const EdgeLaunch& L, hipStream_t st );   // fills e1/e2/ew
 
-// rs_api.hip's runtime state for entry points defined in other translation units (rs_knn.hip)
-int             api_ready( hipStream_t* st );              // ensure_ready(); *st = the calling thread's stream
-void            api_set_err( const char* what );           // rs_hip_last_error()'s text
-const GridView* api_cloud_view( const struct ::rs_hip_cloud* c );
-void*           api_prof_begin();                          // rs_hip_profile_enable: an event on the thread's stream (null: profiling off)
-void            api_prof_end( const char* name, void* begin );   // ... and the span since then, booked under `name`
-// the level builder's gather target, for a producer in another unit (rs_mesh.hip): room for n points (normals: *nor, else null) ...
-int             api_level_workspace( size_t n, bool with_nor, float** pos, float** nor );
-// ... and the cloud over the n points written there (the index build of rs_hip_cloud_create_level); null on failure
-struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float cell_size );
-// a cloud's points for a reader in another unit (rs_fuse.hip): the query layout (Hilbert order, 16-byte records) and the map from an
-// original index to its slot there; nor is null for a cloud without normals
-struct CloudPoints { const float4* qpos; const float4* qnor; const int* by_orig; int n; };
-CloudPoints     api_cloud_points( const struct ::rs_hip_cloud* c );
-
 } // namespace rs

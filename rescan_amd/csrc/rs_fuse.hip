@@ -30,8 +30,7 @@
 //
 // Above 16 384 extracted points the library's ICP is within 1e-4 of the reference's pose, not bit-identical to it, and
 // the merged positions of such an object inherit that difference; everything else here is bit for bit.
-#include "../../include/rescan_hip.h"
-#include "rs_device.h"
+#include "rs_host.h"
 #include "rs_fuse.h"
 
 #include <chrono>
@@ -172,64 +171,37 @@ using namespace rs;
 
 namespace {
 
-struct FuseBuf
-{
-  void* p = nullptr; size_t cap = 0;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-  template <class T> T* as() { return (T*)p; }
-};
-struct FuseWorkspace { FuseBuf key, step, skey, sstep, perm, tmp, point_ids, ids, flags, rank, index, a_pos, a_nor, b_pos, b_nor, out_pos, out_nor; };
+struct FuseWorkspace { Buf key, step, skey, sstep, perm, tmp, point_ids, ids, flags, rank, index, a_pos, a_nor, b_pos, b_nor, out_pos, out_nor; };
 thread_local FuseWorkspace g_fuse_ws;
-
-int fuse_fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-// NOT between api_prof_begin and api_prof_end: the early return would leave the profiling span open
-#define FUSE_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) return fuse_fail( RS_HIP_E_RUNTIME, what, e_ ); } while( 0 )
-
-unsigned fuse_blocks( long long n ) { return (unsigned)std::max<long long>( 1, ( n + FUSE_BLOCK - 1 ) / FUSE_BLOCK ); }
 
 // the permutation of n <= 2^24 elements in the workspace's perm buffer (n >= 1)
 int fuse_permutation_device( int n, uint32_t seed, hipStream_t st )
 {
   FuseWorkspace& W = g_fuse_ws;
   const int m = n - 1;
-  FUSE_TRY( W.perm.ensure( (size_t)n * 4 ), "fuse: buffers" );
+  RS_TRY( W.perm.ensure( (size_t)n * 4 ), "fuse: buffers" );
   const size_t mm = (size_t)std::max( m, 1 );
   int key_bits = 1; while( key_bits < 32 && ( (size_t)1 << key_bits ) < mm ) ++key_bits;      // keys are < m
   const size_t tmp_bytes = build_sort_temp_bytes( (int)mm, key_bits );
-  FUSE_TRY( W.key.ensure( mm * 4 ), "fuse: buffers" ); FUSE_TRY( W.step.ensure( mm * 4 ), "fuse: buffers" );
-  FUSE_TRY( W.skey.ensure( mm * 4 ), "fuse: buffers" ); FUSE_TRY( W.sstep.ensure( mm * 4 ), "fuse: buffers" );
-  FUSE_TRY( W.tmp.ensure( tmp_bytes + 256 ), "fuse: buffers" );
-  void* ev = api_prof_begin();
-  int sort_rc = 0;
-  if( m > 0 )
+  RS_TRY( W.key.ensure( mm * 4 ), "fuse: buffers" ); RS_TRY( W.step.ensure( mm * 4 ), "fuse: buffers" );
+  RS_TRY( W.skey.ensure( mm * 4 ), "fuse: buffers" ); RS_TRY( W.sstep.ensure( mm * 4 ), "fuse: buffers" );
+  RS_TRY( W.tmp.ensure( tmp_bytes + 256 ), "fuse: buffers" );
   {
-    FuseDrawArgs D;
-    D.jump = fuse::jump_table( seed ); D.m = m; D.key = W.key.as<uint32_t>(); D.step = W.step.as<uint32_t>();
-    int bits = 1; while( bits < fuse::JUMP_BITS && ( (uint32_t)( m - 1 ) >> bits ) ) ++bits;
-    D.n_bits = bits;
-    hipLaunchKernelGGL( k_fuse_draw, dim3( fuse_blocks( m ) ), dim3( FUSE_BLOCK ), 0, st, D );
-    // stable, and the steps go in increasing: equal keys keep their steps in increasing order
-    sort_rc = build_sort_pairs( W.tmp.p, tmp_bytes, W.key.as<uint32_t>(), W.skey.as<uint32_t>(), W.step.as<uint32_t>(), W.sstep.as<uint32_t>(), m, key_bits, st );
+    ProfSpan span( "fuse_permutation" );
+    if( m > 0 )
+    {
+      FuseDrawArgs D;
+      D.jump = fuse::jump_table( seed ); D.m = m; D.key = W.key.as<uint32_t>(); D.step = W.step.as<uint32_t>();
+      int bits = 1; while( bits < fuse::JUMP_BITS && ( (uint32_t)( m - 1 ) >> bits ) ) ++bits;
+      D.n_bits = bits;
+      hipLaunchKernelGGL( k_fuse_draw, dim3( blocks_for( m, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, D );
+      // stable, and the steps go in increasing: equal keys keep their steps in increasing order
+      if( build_sort_pairs( W.tmp.p, tmp_bytes, W.key.as<uint32_t>(), W.skey.as<uint32_t>(), W.step.as<uint32_t>(), W.sstep.as<uint32_t>(), m, key_bits, st ) )
+        return fail( RS_HIP_E_RUNTIME, "fuse: device sort failed" );
+    }
+    hipLaunchKernelGGL( k_fuse_walk, dim3( blocks_for( n, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, W.key.as<uint32_t>(), W.skey.as<uint32_t>(), W.sstep.as<uint32_t>(), n, W.perm.as<int32_t>() );
   }
-  if( !sort_rc )
-    hipLaunchKernelGGL( k_fuse_walk, dim3( fuse_blocks( n ) ), dim3( FUSE_BLOCK ), 0, st, W.key.as<uint32_t>(), W.skey.as<uint32_t>(), W.sstep.as<uint32_t>(), n, W.perm.as<int32_t>() );
-  api_prof_end( "fuse_permutation", ev );
-  if( sort_rc ) return fuse_fail( RS_HIP_E_RUNTIME, "fuse: device sort failed" );
-  FUSE_TRY( hipGetLastError(), "fuse: permutation launch" );
+  RS_TRY( hipGetLastError(), "fuse: permutation launch" );
   return RS_HIP_OK;
 }
 
@@ -239,31 +211,32 @@ int fuse_select_device( const int32_t* d_point_ids, int n, const int32_t* ids, i
   FuseWorkspace& W = g_fuse_ws;
   const size_t n1 = (size_t)n + 1;
   const size_t tmp_bytes = build_scan_temp_bytes( n1 );
-  FUSE_TRY( W.ids.ensure( (size_t)n_ids * 4 ), "fuse: buffers" ); FUSE_TRY( W.flags.ensure( n1 * 4 ), "fuse: buffers" );
-  FUSE_TRY( W.rank.ensure( n1 * 4 ), "fuse: buffers" ); FUSE_TRY( W.index.ensure( (size_t)n * 4 ), "fuse: buffers" );
-  FUSE_TRY( W.tmp.ensure( tmp_bytes + 256 ), "fuse: buffers" );
-  FUSE_TRY( hipMemcpyAsync( W.ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, st ), "fuse: upload" );
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_fuse_flag, dim3( fuse_blocks( (long long)n1 ) ), dim3( FUSE_BLOCK ), 0, st, d_point_ids, n, W.ids.as<int32_t>(), n_ids, W.flags.as<uint32_t>() );
-  const int scan_rc = build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st );
-  if( !scan_rc )
-    hipLaunchKernelGGL( k_fuse_scatter, dim3( fuse_blocks( n ) ), dim3( FUSE_BLOCK ), 0, st, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n, W.index.as<int32_t>() );
-  api_prof_end( "fuse_select", ev );
-  if( scan_rc ) return fuse_fail( RS_HIP_E_RUNTIME, "fuse: device scan failed" );
-  FUSE_TRY( hipGetLastError(), "fuse: select launch" );
+  RS_TRY( W.ids.ensure( (size_t)n_ids * 4 ), "fuse: buffers" ); RS_TRY( W.flags.ensure( n1 * 4 ), "fuse: buffers" );
+  RS_TRY( W.rank.ensure( n1 * 4 ), "fuse: buffers" ); RS_TRY( W.index.ensure( (size_t)n * 4 ), "fuse: buffers" );
+  RS_TRY( W.tmp.ensure( tmp_bytes + 256 ), "fuse: buffers" );
+  RS_TRY( hipMemcpyAsync( W.ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, st ), "fuse: upload" );
+  {
+    ProfSpan span( "fuse_select" );
+    hipLaunchKernelGGL( k_fuse_flag, dim3( blocks_for( (long long)n1, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, d_point_ids, n, W.ids.as<int32_t>(), n_ids, W.flags.as<uint32_t>() );
+    if( build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st ) )
+      return fail( RS_HIP_E_RUNTIME, "fuse: device scan failed" );
+    hipLaunchKernelGGL( k_fuse_scatter, dim3( blocks_for( n, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n, W.index.as<int32_t>() );
+  }
+  RS_TRY( hipGetLastError(), "fuse: select launch" );
   uint32_t got = 0;
-  FUSE_TRY( hipMemcpyAsync( &got, W.rank.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ), "fuse: download" );
-  FUSE_TRY( hipStreamSynchronize( st ), "fuse: select" );
+  RS_TRY( hipMemcpyAsync( &got, W.rank.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ), "fuse: download" );
+  RS_TRY( hipStreamSynchronize( st ), "fuse: select" );
   *count = (int64_t)got;
   return RS_HIP_OK;
 }
 
 int fuse_merge_launch( const FuseMergeArgs& A, hipStream_t st )
 {
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_fuse_merge, dim3( fuse_blocks( A.n ) ), dim3( FUSE_BLOCK ), 0, st, A );
-  api_prof_end( "fuse_merge", ev );
-  FUSE_TRY( hipGetLastError(), "fuse: merge launch" );
+  {
+    ProfSpan span( "fuse_merge" );
+    hipLaunchKernelGGL( k_fuse_merge, dim3( blocks_for( A.n, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, A );
+  }
+  RS_TRY( hipGetLastError(), "fuse: merge launch" );
   return RS_HIP_OK;
 }
 
@@ -282,36 +255,36 @@ int rs_hip_shuffle_plan( int64_t n, uint32_t seed, int32_t* perm )
 int rs_hip_shuffle_permutation( int64_t n, uint32_t seed, int32_t* perm )
 {
   char err[256] = "";
-  if( int rc = fuse::check_size( n, err, sizeof(err) ) ) return fuse_fail( rc, err );
-  if( n > 0 && !perm ) return fuse_fail( RS_HIP_E_ARG, "shuffle_permutation: no array for the permutation" );
+  if( int rc = fuse::check_size( n, err, sizeof(err) ) ) return fail( rc, err );
+  if( n > 0 && !perm ) return fail( RS_HIP_E_ARG, "shuffle_permutation: no array for the permutation" );
   if( n == 0 ) return RS_HIP_OK;
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   rc = fuse_permutation_device( (int)n, seed, st ); if( rc ) return rc;
-  FUSE_TRY( hipMemcpyAsync( perm, g_fuse_ws.perm.p, (size_t)n * 4, hipMemcpyDeviceToHost, st ), "shuffle_permutation: download" );
-  FUSE_TRY( hipStreamSynchronize( st ), "shuffle_permutation: kernels" );
+  RS_TRY( hipMemcpyAsync( perm, g_fuse_ws.perm.p, (size_t)n * 4, hipMemcpyDeviceToHost, st ), "shuffle_permutation: download" );
+  RS_TRY( hipStreamSynchronize( st ), "shuffle_permutation: kernels" );
   return RS_HIP_OK;
 }
 
 int rs_hip_select_by_ids( const int32_t* point_ids, int64_t n, const int32_t* ids, int32_t n_ids, int32_t* index, int64_t* count )
 {
   char err[256] = "";
-  if( !count || n < 0 || ( n > 0 && ( !point_ids || !index ) ) ) return fuse_fail( RS_HIP_E_ARG, "select_by_ids: null arrays or a negative count" );
-  if( n > 2147483646ll ) return fuse_fail( RS_HIP_E_CAPACITY, "select_by_ids: more points than an int32 index can name" );
-  if( int rc = fuse::check_ids( ids, n_ids, err, sizeof(err) ) ) return fuse_fail( rc, err );
+  if( !count || n < 0 || ( n > 0 && ( !point_ids || !index ) ) ) return fail( RS_HIP_E_ARG, "select_by_ids: null arrays or a negative count" );
+  if( n > 2147483646ll ) return fail( RS_HIP_E_CAPACITY, "select_by_ids: more points than an int32 index can name" );
+  if( int rc = fuse::check_ids( ids, n_ids, err, sizeof(err) ) ) return fail( rc, err );
   *count = 0;
   if( n == 0 || n_ids == 0 ) return RS_HIP_OK;
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   FuseWorkspace& W = g_fuse_ws;
-  FUSE_TRY( W.point_ids.ensure( (size_t)n * 4 ), "select_by_ids: buffers" );
-  FUSE_TRY( hipMemcpyAsync( W.point_ids.p, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, st ), "select_by_ids: upload" );
+  RS_TRY( W.point_ids.ensure( (size_t)n * 4 ), "select_by_ids: buffers" );
+  RS_TRY( hipMemcpyAsync( W.point_ids.p, point_ids, (size_t)n * 4, hipMemcpyHostToDevice, st ), "select_by_ids: upload" );
   int64_t got = 0;
   rc = fuse_select_device( W.point_ids.as<int32_t>(), (int)n, ids, n_ids, &got, st ); if( rc ) return rc;
   if( got > 0 )
   {
-    FUSE_TRY( hipMemcpyAsync( index, W.index.p, (size_t)got * 4, hipMemcpyDeviceToHost, st ), "select_by_ids: download" );
-    FUSE_TRY( hipStreamSynchronize( st ), "select_by_ids: download" );
+    RS_TRY( hipMemcpyAsync( index, W.index.p, (size_t)got * 4, hipMemcpyDeviceToHost, st ), "select_by_ids: download" );
+    RS_TRY( hipStreamSynchronize( st ), "select_by_ids: download" );
   }
   *count = got;
   return RS_HIP_OK;
@@ -322,29 +295,29 @@ int rs_hip_merge_shuffled( const float* a_pos, const float* a_nor, int64_t n_a, 
                            float* out_pos, float* out_nor, int32_t* source )
 {
   char err[256] = "";
-  if( n_a < 0 || n_b < 0 ) return fuse_fail( RS_HIP_E_ARG, "merge_shuffled: a negative count" );
-  if( n_a > fuse::MAX_POINTS || n_b > fuse::MAX_POINTS ) return fuse_fail( RS_HIP_E_CAPACITY, "merge_shuffled: more than 2^24 points" );
+  if( n_a < 0 || n_b < 0 ) return fail( RS_HIP_E_ARG, "merge_shuffled: a negative count" );
+  if( n_a > fuse::MAX_POINTS || n_b > fuse::MAX_POINTS ) return fail( RS_HIP_E_CAPACITY, "merge_shuffled: more than 2^24 points" );
   const int64_t n = n_a + n_b;
-  if( int rc = fuse::check_size( n, err, sizeof(err) ) ) return fuse_fail( rc, err );
+  if( int rc = fuse::check_size( n, err, sizeof(err) ) ) return fail( rc, err );
   if( !xform || ( n_a > 0 && ( !a_pos || !a_nor ) ) || ( n_b > 0 && ( !b_pos || !b_nor ) ) || ( n > 0 && ( !out_pos || !out_nor ) ) )
-    return fuse_fail( RS_HIP_E_ARG, "merge_shuffled: null arrays (both clouds need normals)" );
+    return fail( RS_HIP_E_ARG, "merge_shuffled: null arrays (both clouds need normals)" );
   if( n == 0 ) return RS_HIP_OK;
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   FuseWorkspace& W = g_fuse_ws;
   const size_t ba = (size_t)n_a * 12, bb = (size_t)n_b * 12, bo = (size_t)n * 12;
-  FUSE_TRY( W.a_pos.ensure( std::max<size_t>( ba, 12 ) ), "merge_shuffled: buffers" ); FUSE_TRY( W.a_nor.ensure( std::max<size_t>( ba, 12 ) ), "merge_shuffled: buffers" );
-  FUSE_TRY( W.b_pos.ensure( std::max<size_t>( bb, 12 ) ), "merge_shuffled: buffers" ); FUSE_TRY( W.b_nor.ensure( std::max<size_t>( bb, 12 ) ), "merge_shuffled: buffers" );
-  FUSE_TRY( W.out_pos.ensure( bo ), "merge_shuffled: buffers" ); FUSE_TRY( W.out_nor.ensure( bo ), "merge_shuffled: buffers" );
+  RS_TRY( W.a_pos.ensure( std::max<size_t>( ba, 12 ) ), "merge_shuffled: buffers" ); RS_TRY( W.a_nor.ensure( std::max<size_t>( ba, 12 ) ), "merge_shuffled: buffers" );
+  RS_TRY( W.b_pos.ensure( std::max<size_t>( bb, 12 ) ), "merge_shuffled: buffers" ); RS_TRY( W.b_nor.ensure( std::max<size_t>( bb, 12 ) ), "merge_shuffled: buffers" );
+  RS_TRY( W.out_pos.ensure( bo ), "merge_shuffled: buffers" ); RS_TRY( W.out_nor.ensure( bo ), "merge_shuffled: buffers" );
   if( n_a > 0 )
   {
-    FUSE_TRY( hipMemcpyAsync( W.a_pos.p, a_pos, ba, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
-    FUSE_TRY( hipMemcpyAsync( W.a_nor.p, a_nor, ba, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
+    RS_TRY( hipMemcpyAsync( W.a_pos.p, a_pos, ba, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
+    RS_TRY( hipMemcpyAsync( W.a_nor.p, a_nor, ba, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
   }
   if( n_b > 0 )
   {
-    FUSE_TRY( hipMemcpyAsync( W.b_pos.p, b_pos, bb, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
-    FUSE_TRY( hipMemcpyAsync( W.b_nor.p, b_nor, bb, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
+    RS_TRY( hipMemcpyAsync( W.b_pos.p, b_pos, bb, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
+    RS_TRY( hipMemcpyAsync( W.b_nor.p, b_nor, bb, hipMemcpyHostToDevice, st ), "merge_shuffled: upload" );
   }
   rc = fuse_permutation_device( (int)n, seed, st ); if( rc ) return rc;
   FuseMergeArgs A{};
@@ -352,10 +325,10 @@ int rs_hip_merge_shuffled( const float* a_pos, const float* a_nor, int64_t n_a, 
   A.n_a = (int)n_a; A.n = (int)n; std::memcpy( A.x.m, xform, 64 );
   A.perm = W.perm.as<int32_t>(); A.out_pos = W.out_pos.as<float>(); A.out_nor = W.out_nor.as<float>();
   rc = fuse_merge_launch( A, st ); if( rc ) return rc;
-  FUSE_TRY( hipMemcpyAsync( out_pos, W.out_pos.p, bo, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
-  FUSE_TRY( hipMemcpyAsync( out_nor, W.out_nor.p, bo, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
-  if( source ) FUSE_TRY( hipMemcpyAsync( source, W.perm.p, (size_t)n * 4, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
-  FUSE_TRY( hipStreamSynchronize( st ), "merge_shuffled: kernels" );
+  RS_TRY( hipMemcpyAsync( out_pos, W.out_pos.p, bo, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
+  RS_TRY( hipMemcpyAsync( out_nor, W.out_nor.p, bo, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
+  if( source ) RS_TRY( hipMemcpyAsync( source, W.perm.p, (size_t)n * 4, hipMemcpyDeviceToHost, st ), "merge_shuffled: download" );
+  RS_TRY( hipStreamSynchronize( st ), "merge_shuffled: kernels" );
   return RS_HIP_OK;
 }
 
@@ -375,7 +348,7 @@ rs_hip_cloud_t* rs_hip_cloud_create_fused( const rs_hip_cloud_t* scan, const int
                                            float max_dist, float max_angle, float cell_size,
                                            float xform_out[16], float* icp_err, int32_t* source, int32_t* scan_index, int64_t* n_extracted )
 {
-  auto refuse = []( int rc, const char* what ) { fuse_fail( rc, what ); return (rs_hip_cloud_t*)nullptr; };
+  auto refuse = []( int rc, const char* what ) { fail( rc, what ); return (rs_hip_cloud_t*)nullptr; };
   if( n_extracted ) *n_extracted = 0;
   if( !scan || !model || !pose ) return refuse( RS_HIP_E_ARG, "cloud_create_fused: scan, model and pose are required" );
   const CloudPoints S = api_cloud_points( scan ), M = api_cloud_points( model );
@@ -420,7 +393,7 @@ rs_hip_cloud_t* rs_hip_cloud_create_fused( const rs_hip_cloud_t* scan, const int
   {
     float *d_pos = nullptr, *d_nor = nullptr;
     if( api_level_workspace( (size_t)n_a, true, &d_pos, &d_nor ) ) return nullptr;
-    hipLaunchKernelGGL( k_fuse_gather, dim3( fuse_blocks( n_a ) ), dim3( FUSE_BLOCK ), 0, st, A, (int)n_a, d_pos, d_nor );
+    hipLaunchKernelGGL( k_fuse_gather, dim3( blocks_for( n_a, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, A, (int)n_a, d_pos, d_nor );
     FUSED_TRY( hipGetLastError(), "cloud_create_fused: gather launch" );
     rs_hip_cloud_t* src = api_cloud_from_level_workspace( true, (int32_t)n_a, -1.0f );
     if( !src ) return nullptr;

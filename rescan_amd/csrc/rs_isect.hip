@@ -35,7 +35,7 @@
 // score < 0.01f) or disjoint boxes settle, and evaluates the remaining (keep, i) pairs in ONE launch with one small
 // read-back (12 bytes per pair).  Skipping the overlap where a cheap test already discards changes no mark: the reference
 // ORs the three tests (:422).
-#include "../../include/rescan_hip.h"
+#include "rs_host.h"
 #include "rs_search.h"
 
 #include <algorithm>
@@ -190,32 +190,10 @@ __global__ __launch_bounds__( ISECT_BLOCK ) void k_isect( const IsectPair* pairs
 
 // ------------------------------------------------------------------------------------------
 
-struct IsectBuf
-{
-  void* p = nullptr; size_t cap = 0; bool pinned = false;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = pinned ? hipHostFree( p ) : hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = pinned ? hipHostMalloc( &p, want, hipHostMallocDefault ) : hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-};
-struct IsectWorkspace { IsectBuf jobs, boxes, pairs, list, out, slab, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true }; };
+struct IsectWorkspace { Buf jobs, boxes, pairs, list, out, slab, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true }; };
 thread_local IsectWorkspace g_isect_ws;
 int g_isect_lds_bytes = ISECT_LDS_BYTES;
 int64_t g_isect_evaluated = 0, g_isect_skipped = 0;
-
-int fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-#define ISECT_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) return fail( RS_HIP_E_RUNTIME, what, e_ ); } while( 0 )
 
 struct HostShape { const GridView* boundary; const GridView* extent; };
 
@@ -232,21 +210,20 @@ int run_boxes( const std::vector<IsectBoxJob>& jobs, float* boxes, hipStream_t s
   IsectWorkspace& W = g_isect_ws;
   const size_t n = jobs.size();
   if( !n ) return RS_HIP_OK;
-  ISECT_TRY( W.jobs.ensure( n * sizeof(IsectBoxJob) ), "isect: buffers" );
-  ISECT_TRY( W.boxes.ensure( n * 24 ), "isect: buffers" );
-  ISECT_TRY( W.h_in.ensure( n * sizeof(IsectBoxJob) ), "isect: buffers" );
-  ISECT_TRY( W.h_out.ensure( n * 24 ), "isect: buffers" );
+  RS_TRY( W.jobs.ensure( n * sizeof(IsectBoxJob) ), "isect: buffers" );
+  RS_TRY( W.boxes.ensure( n * 24 ), "isect: buffers" );
+  RS_TRY( W.h_in.ensure( n * sizeof(IsectBoxJob) ), "isect: buffers" );
+  RS_TRY( W.h_out.ensure( n * 24 ), "isect: buffers" );
   std::memcpy( W.h_in.p, jobs.data(), n * sizeof(IsectBoxJob) );
-  ISECT_TRY( hipMemcpyAsync( W.jobs.p, W.h_in.p, n * sizeof(IsectBoxJob), hipMemcpyHostToDevice, st ), "isect: upload" );
+  RS_TRY( hipMemcpyAsync( W.jobs.p, W.h_in.p, n * sizeof(IsectBoxJob), hipMemcpyHostToDevice, st ), "isect: upload" );
   {
-    void* ev = api_prof_begin();
-    hipLaunchKernelGGL( k_isect_boxes, dim3( (unsigned)( ( n + ISECT_BLOCK / 64 - 1 ) / ( ISECT_BLOCK / 64 ) ) ), dim3( ISECT_BLOCK ), 0, st,
+    ProfSpan span( "isect" );
+    hipLaunchKernelGGL( k_isect_boxes, dim3( blocks_for( (long long)n, ISECT_BLOCK / 64 ) ), dim3( ISECT_BLOCK ), 0, st,
                         (const IsectBoxJob*)W.jobs.p, (int)n, (float*)W.boxes.p );
-    api_prof_end( "isect", ev );
   }
-  ISECT_TRY( hipGetLastError(), "isect: boxes launch" );
-  ISECT_TRY( hipMemcpyAsync( W.h_out.p, W.boxes.p, n * 24, hipMemcpyDeviceToHost, st ), "isect: download" );
-  ISECT_TRY( hipStreamSynchronize( st ), "isect: boxes" );
+  RS_TRY( hipGetLastError(), "isect: boxes launch" );
+  RS_TRY( hipMemcpyAsync( W.h_out.p, W.boxes.p, n * 24, hipMemcpyDeviceToHost, st ), "isect: download" );
+  RS_TRY( hipStreamSynchronize( st ), "isect: boxes" );
   std::memcpy( boxes, W.h_out.p, n * 24 );
   return RS_HIP_OK;
 }
@@ -327,34 +304,35 @@ int run_pairs( const std::vector<PairIn>& in, float voxel, int fill, int32_t* co
   }
   const size_t np = pairs.size(), nl = lds_list.size() + glb_list.size();
   const size_t in_bytes = np * sizeof(IsectPair) + nl * 4, out_bytes = n * 16;      // counts x 3 + status
-  ISECT_TRY( W.pairs.ensure( np * sizeof(IsectPair) ), "isect: buffers" );
-  ISECT_TRY( W.list.ensure( nl * 4 ), "isect: buffers" );
-  ISECT_TRY( W.out.ensure( out_bytes ), "isect: buffers" );
-  ISECT_TRY( W.h_in.ensure( in_bytes ), "isect: buffers" );
-  ISECT_TRY( W.h_out.ensure( out_bytes ), "isect: buffers" );
-  if( slab_bytes ) ISECT_TRY( W.slab.ensure( slab_bytes ), "isect: scratch slab" );
+  RS_TRY( W.pairs.ensure( np * sizeof(IsectPair) ), "isect: buffers" );
+  RS_TRY( W.list.ensure( nl * 4 ), "isect: buffers" );
+  RS_TRY( W.out.ensure( out_bytes ), "isect: buffers" );
+  RS_TRY( W.h_in.ensure( in_bytes ), "isect: buffers" );
+  RS_TRY( W.h_out.ensure( out_bytes ), "isect: buffers" );
+  if( slab_bytes ) RS_TRY( W.slab.ensure( slab_bytes ), "isect: scratch slab" );
   char* h = (char*)W.h_in.p;
   std::memcpy( h, pairs.data(), np * sizeof(IsectPair) );
   int* hl = (int*)( h + np * sizeof(IsectPair) );
   std::copy( lds_list.begin(), lds_list.end(), hl ); std::copy( glb_list.begin(), glb_list.end(), hl + lds_list.size() );
-  ISECT_TRY( hipMemcpyAsync( W.pairs.p, h, np * sizeof(IsectPair), hipMemcpyHostToDevice, st ), "isect: upload" );
-  ISECT_TRY( hipMemcpyAsync( W.list.p, hl, nl * 4, hipMemcpyHostToDevice, st ), "isect: upload" );
-  ISECT_TRY( hipMemsetAsync( W.out.p, 0, out_bytes, st ), "isect: clear" );
+  RS_TRY( hipMemcpyAsync( W.pairs.p, h, np * sizeof(IsectPair), hipMemcpyHostToDevice, st ), "isect: upload" );
+  RS_TRY( hipMemcpyAsync( W.list.p, hl, nl * 4, hipMemcpyHostToDevice, st ), "isect: upload" );
+  RS_TRY( hipMemsetAsync( W.out.p, 0, out_bytes, st ), "isect: clear" );
   int* d_counts = (int*)W.out.p; int* d_status = d_counts + 3 * n;
-  void* ev = api_prof_begin();
-  if( !lds_list.empty() )
   {
-    const size_t dyn = ( std::max<size_t>( lds_max, 1024 ) + 1023 ) / 1024 * 1024;     // whole KB: a few launch shapes only
-    hipLaunchKernelGGL( k_isect<false>, dim3( (unsigned)lds_list.size() ), dim3( ISECT_BLOCK ), dyn, st,
-                        (const IsectPair*)W.pairs.p, (const int*)W.list.p, (uint32_t*)nullptr, fill, d_counts, d_status );
+    ProfSpan span( "isect" );
+    if( !lds_list.empty() )
+    {
+      const size_t dyn = ( std::max<size_t>( lds_max, 1024 ) + 1023 ) / 1024 * 1024;     // whole KB: a few launch shapes only
+      hipLaunchKernelGGL( k_isect<false>, dim3( (unsigned)lds_list.size() ), dim3( ISECT_BLOCK ), dyn, st,
+                          (const IsectPair*)W.pairs.p, (const int*)W.list.p, (uint32_t*)nullptr, fill, d_counts, d_status );
+    }
+    for( const auto& c : glb_chunks )
+      hipLaunchKernelGGL( k_isect<true>, dim3( (unsigned)( c.second - c.first ) ), dim3( ISECT_BLOCK ), 0, st,
+                          (const IsectPair*)W.pairs.p, (const int*)W.list.p + lds_list.size() + c.first, (uint32_t*)W.slab.p, fill, d_counts, d_status );
   }
-  for( const auto& c : glb_chunks )
-    hipLaunchKernelGGL( k_isect<true>, dim3( (unsigned)( c.second - c.first ) ), dim3( ISECT_BLOCK ), 0, st,
-                        (const IsectPair*)W.pairs.p, (const int*)W.list.p + lds_list.size() + c.first, (uint32_t*)W.slab.p, fill, d_counts, d_status );
-  api_prof_end( "isect", ev );
-  ISECT_TRY( hipGetLastError(), "isect: launch" );
-  ISECT_TRY( hipMemcpyAsync( W.h_out.p, W.out.p, out_bytes, hipMemcpyDeviceToHost, st ), "isect: download" );
-  ISECT_TRY( hipStreamSynchronize( st ), "isect" );
+  RS_TRY( hipGetLastError(), "isect: launch" );
+  RS_TRY( hipMemcpyAsync( W.h_out.p, W.out.p, out_bytes, hipMemcpyDeviceToHost, st ), "isect: download" );
+  RS_TRY( hipStreamSynchronize( st ), "isect" );
   const int* hc = (const int*)W.h_out.p; const int* hs = hc + 3 * n;
   for( size_t k = 0; k < n; ++k )
     if( hs[k] )

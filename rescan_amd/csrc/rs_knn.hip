@@ -18,7 +18,7 @@
 //   more than 128 bins, fewer than k points, a query outside the box) the answer is KnnGrid's: no bin cap, and the walk ends once
 //   every bin has been visited.
 
-#include "../../include/rescan_hip.h"
+#include "rs_host.h"
 #include "rs_search.h"
 
 #include <algorithm>
@@ -305,30 +305,8 @@ struct rs_hip_knn_grid
 
 namespace {
 
-struct KnnBuf
-{
-  void* p = nullptr; size_t cap = 0; bool pinned = false;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = pinned ? hipHostFree( p ) : hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = pinned ? hipHostMalloc( &p, want, hipHostMallocDefault ) : hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-};
-struct KnnWorkspace { KnnBuf q, rows, h_q{ nullptr, 0, true }, h_rows{ nullptr, 0, true }; };
+struct KnnWorkspace { Buf q, rows, h_q{ nullptr, 0, true }, h_rows{ nullptr, 0, true }; };
 thread_local KnnWorkspace g_knn_ws;
-
-int fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-#define KNN_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) return fail( RS_HIP_E_RUNTIME, what, e_ ); } while( 0 )
 
 void host_box( const float* pos, int64_t n, int32_t dim, float mn[3], float mx[3] )
 {
@@ -349,9 +327,9 @@ int build_grid( rs_hip_knn_grid* G, const GridView& c, float radius, int32_t dim
   if( n > 0 )
   {
     unsigned* d_box = nullptr;
-    KNN_TRY( hipMalloc( (void**)&d_box, 24 ), "knn grid: bounds" );
+    RS_TRY( hipMalloc( (void**)&d_box, 24 ), "knn grid: bounds" );
     hipError_t e = hipMemcpyAsync( d_box, box, 24, hipMemcpyHostToDevice, st );
-    if( e == hipSuccess ) { hipLaunchKernelGGL( k_knn_bounds, dim3( std::min( 1024, ( n + KNN_BLOCK - 1 ) / KNN_BLOCK ) ), dim3( KNN_BLOCK ), 0, st, c.pos, n, d_box ); e = hipGetLastError(); }
+    if( e == hipSuccess ) { hipLaunchKernelGGL( k_knn_bounds, dim3( std::min( 1024u, blocks_for( n, KNN_BLOCK ) ) ), dim3( KNN_BLOCK ), 0, st, c.pos, n, d_box ); e = hipGetLastError(); }
     if( e == hipSuccess ) e = hipMemcpyAsync( box, d_box, 24, hipMemcpyDeviceToHost, st );
     if( e == hipSuccess ) e = hipStreamSynchronize( st );
     (void)hipFree( d_box );
@@ -378,8 +356,8 @@ int build_grid( rs_hip_knn_grid* G, const GridView& c, float radius, int32_t dim
   v.minx = g.min_pt[0]; v.miny = g.min_pt[1]; v.minz = g.min_pt[2];
   v.inv_cell = g.inv_cell; v.cs = (float)g.cell;
   v.w = (int)g.w; v.h = (int)g.h; v.d = (int)g.d; v.last_layer = (int)std::max( g.w, std::max( g.h, g.d ) ); v.n = n;
-  KNN_TRY( hipMalloc( (void**)&G->d_start, ( n_bins + 1 ) * 4 ), "knn grid: offset table" );
-  KNN_TRY( hipMalloc( (void**)&G->d_rec, (size_t)std::max( n, 1 ) * 16 ), "knn grid: records" );
+  RS_TRY( hipMalloc( (void**)&G->d_start, ( n_bins + 1 ) * 4 ), "knn grid: offset table" );
+  RS_TRY( hipMalloc( (void**)&G->d_rec, (size_t)std::max( n, 1 ) * 16 ), "knn grid: records" );
   v.rec = G->d_rec; v.start = G->d_start;
   // counting sort: histogram (each point's rank inside its bin from the same atomic) -> exclusive scan -> scatter
   uint32_t *counts = nullptr, *bin_of = nullptr, *rank = nullptr; void* tmp = nullptr;
@@ -391,15 +369,13 @@ int build_grid( rs_hip_knn_grid* G, const GridView& c, float radius, int32_t dim
   if( e == hipSuccess ) e = hipMemsetAsync( counts, 0, ( n_bins + 1 ) * 4, st );
   if( e == hipSuccess && n > 0 )
   {
-    const int blocks = ( n + KNN_BLOCK - 1 ) / KNN_BLOCK;
-    hipLaunchKernelGGL( k_knn_count, dim3( blocks ), dim3( KNN_BLOCK ), 0, st, c.pos, n, v, bin_of, rank, counts );
+    hipLaunchKernelGGL( k_knn_count, dim3( blocks_for( n, KNN_BLOCK ) ), dim3( KNN_BLOCK ), 0, st, c.pos, n, v, bin_of, rank, counts );
     e = hipGetLastError();
   }
   if( e == hipSuccess && build_exclusive_scan( tmp, tmp_bytes, counts, G->d_start, n_bins + 1, st ) ) e = hipErrorUnknown;
   if( e == hipSuccess && n > 0 )
   {
-    const int blocks = ( n + KNN_BLOCK - 1 ) / KNN_BLOCK;
-    hipLaunchKernelGGL( k_knn_scatter, dim3( blocks ), dim3( KNN_BLOCK ), 0, st, c.pos, n, bin_of, rank, G->d_start, G->d_rec );
+    hipLaunchKernelGGL( k_knn_scatter, dim3( blocks_for( n, KNN_BLOCK ) ), dim3( KNN_BLOCK ), 0, st, c.pos, n, bin_of, rank, G->d_start, G->d_rec );
     e = hipGetLastError();
   }
   if( e == hipSuccess ) e = hipStreamSynchronize( st );
@@ -474,10 +450,10 @@ int rs_hip_knn_search( const rs_hip_knn_grid_t* grid, const float* query, int64_
   KnnWorkspace& W = g_knn_ws;
   const int64_t first = std::min( chunk, n_query );
   const size_t row_words = (size_t)first * k * 2 + (size_t)first;
-  KNN_TRY( W.q.ensure( (size_t)first * 12 ), "knn_search: buffers" );
-  KNN_TRY( W.rows.ensure( row_words * 4 ), "knn_search: buffers" );
-  KNN_TRY( W.h_q.ensure( (size_t)first * 12 ), "knn_search: buffers" );
-  KNN_TRY( W.h_rows.ensure( row_words * 4 ), "knn_search: buffers" );
+  RS_TRY( W.q.ensure( (size_t)first * 12 ), "knn_search: buffers" );
+  RS_TRY( W.rows.ensure( row_words * 4 ), "knn_search: buffers" );
+  RS_TRY( W.h_q.ensure( (size_t)first * 12 ), "knn_search: buffers" );
+  RS_TRY( W.h_rows.ensure( row_words * 4 ), "knn_search: buffers" );
   uint64_t tot = 0;
   for( int64_t q0 = 0; q0 < n_query; q0 += chunk )
   {
@@ -485,12 +461,12 @@ int rs_hip_knn_search( const rs_hip_knn_grid_t* grid, const float* query, int64_
     const size_t nk = (size_t)nc * k;
     std::memcpy( W.h_q.p, query + 3 * q0, (size_t)nc * 12 );
     float* d_d2 = (float*)W.rows.p; int* d_idx = (int*)W.rows.p + nk; int* d_n = (int*)W.rows.p + 2 * nk;
-    KNN_TRY( hipMemcpyAsync( W.q.p, W.h_q.p, (size_t)nc * 12, hipMemcpyHostToDevice, st ), "knn_search: upload" );
+    RS_TRY( hipMemcpyAsync( W.q.p, W.h_q.p, (size_t)nc * 12, hipMemcpyHostToDevice, st ), "knn_search: upload" );
     hipLaunchKernelGGL( k_knn, dim3( ( nc + KNN_BLOCK / WAVE - 1 ) / ( KNN_BLOCK / WAVE ) ), dim3( KNN_BLOCK ), 0, st,
                         grid->view, (const float*)W.q.p, nc, (int)k, d_d2, d_idx, d_n );
-    KNN_TRY( hipGetLastError(), "knn_search: launch" );
-    KNN_TRY( hipMemcpyAsync( W.h_rows.p, W.rows.p, ( 2 * nk + nc ) * 4, hipMemcpyDeviceToHost, st ), "knn_search: download" );
-    KNN_TRY( hipStreamSynchronize( st ), "knn_search" );
+    RS_TRY( hipGetLastError(), "knn_search: launch" );
+    RS_TRY( hipMemcpyAsync( W.h_rows.p, W.rows.p, ( 2 * nk + nc ) * 4, hipMemcpyDeviceToHost, st ), "knn_search: download" );
+    RS_TRY( hipStreamSynchronize( st ), "knn_search" );
     // rows are handed over up to their counts only (the caller's arrays keep whatever else they held, like the reference's);
     // runs of full rows in one copy each
     const float* hd = (const float*)W.h_rows.p; const int* hi = (const int*)W.h_rows.p + nk; const int* hn = (const int*)W.h_rows.p + 2 * nk;

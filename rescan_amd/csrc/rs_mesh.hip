@@ -20,8 +20,7 @@
 //                            lane's result depends on the launch geometry or on the window.
 // The fp32 arithmetic matches the reference's because the library is built with -ffp-contract=off and hipcc's default
 // correctly rounded fp32 divide and square root.
-#include "../../include/rescan_hip.h"
-#include "rs_device.h"
+#include "rs_host.h"
 #include "rs_mesh.h"
 
 #include <algorithm>
@@ -137,30 +136,8 @@ using namespace rs;
 
 namespace {
 
-struct MeshBuf
-{
-  void* p = nullptr; size_t cap = 0;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-};
-struct MeshWorkspace { MeshBuf vert, faces, table, out[7]; };
+struct MeshWorkspace { Buf vert, faces, table, out[7]; };
 thread_local MeshWorkspace g_mesh_ws;
-
-int mesh_fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-#define MESH_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) return mesh_fail( RS_HIP_E_RUNTIME, what, e_ ); } while( 0 )
 
 struct MeshIn
 {
@@ -175,7 +152,7 @@ int mesh_prepare( const MeshIn& M, int64_t* n_samples, MeshSampleArgs& A, hipStr
   if( M.n_faces > mesh::MAX_FACES ) { prob.clear(); alias.clear(); }        // (refused below, before the table)
   int rc = mesh::plan( M.pos, M.n_vertices, M.faces, M.n_faces, n_samples, nullptr, prob.empty() ? nullptr : prob.data(),
                        alias.empty() ? nullptr : alias.data(), err, sizeof(err) );
-  if( rc ) return mesh_fail( rc, err );
+  if( rc ) return fail( rc, err );
   rc = api_ready( st ); if( rc ) return rc;
   MeshWorkspace& W = g_mesh_ws;
   const size_t nv = (size_t)M.n_vertices, nf = (size_t)M.n_faces;
@@ -190,13 +167,13 @@ int mesh_prepare( const MeshIn& M, int64_t* n_samples, MeshSampleArgs& A, hipStr
   }
   std::vector<MeshAlias> tab( nf );
   for( size_t i = 0; i < nf; ++i ) { tab[i].prob = prob[i]; tab[i].alias = alias[i]; tab[i].pad = 0; }
-  MESH_TRY( W.vert.ensure( nv * sizeof(MeshVertex) ), "resample: buffers" );
-  MESH_TRY( W.faces.ensure( nf * 12 ), "resample: buffers" );
-  MESH_TRY( W.table.ensure( nf * sizeof(MeshAlias) ), "resample: buffers" );
-  MESH_TRY( hipMemcpyAsync( W.vert.p, rec.data(), nv * sizeof(MeshVertex), hipMemcpyHostToDevice, *st ), "resample: upload" );
-  MESH_TRY( hipMemcpyAsync( W.faces.p, M.faces, nf * 12, hipMemcpyHostToDevice, *st ), "resample: upload" );
-  MESH_TRY( hipMemcpyAsync( W.table.p, tab.data(), nf * sizeof(MeshAlias), hipMemcpyHostToDevice, *st ), "resample: upload" );
-  MESH_TRY( hipStreamSynchronize( *st ), "resample: upload" );          // the staging vectors go out of scope below
+  RS_TRY( W.vert.ensure( nv * sizeof(MeshVertex) ), "resample: buffers" );
+  RS_TRY( W.faces.ensure( nf * 12 ), "resample: buffers" );
+  RS_TRY( W.table.ensure( nf * sizeof(MeshAlias) ), "resample: buffers" );
+  RS_TRY( hipMemcpyAsync( W.vert.p, rec.data(), nv * sizeof(MeshVertex), hipMemcpyHostToDevice, *st ), "resample: upload" );
+  RS_TRY( hipMemcpyAsync( W.faces.p, M.faces, nf * 12, hipMemcpyHostToDevice, *st ), "resample: upload" );
+  RS_TRY( hipMemcpyAsync( W.table.p, tab.data(), nf * sizeof(MeshAlias), hipMemcpyHostToDevice, *st ), "resample: upload" );
+  RS_TRY( hipStreamSynchronize( *st ), "resample: upload" );          // the staging vectors go out of scope below
   A = MeshSampleArgs{};
   A.vert = (const MeshVertex*)W.vert.p; A.faces = (const int32_t*)W.faces.p; A.table = (const MeshAlias*)W.table.p;
   A.n_faces = (int32_t)M.n_faces;
@@ -211,10 +188,11 @@ int mesh_launch( MeshSampleArgs& A, int64_t first, int64_t count, hipStream_t st
   const uint64_t last_steps = 2ull * (uint64_t)( first + count - 1 );
   int bits = 1; while( bits < mesh::JUMP_BITS && ( last_steps >> bits ) ) ++bits;
   A.n_bits = bits;
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_mesh_sample, dim3( (unsigned)( ( count + MESH_BLOCK - 1 ) / MESH_BLOCK ) ), dim3( MESH_BLOCK ), 0, st, A );
-  api_prof_end( "mesh_sample", ev );
-  MESH_TRY( hipGetLastError(), "resample: launch" );
+  {
+    ProfSpan span( "mesh_sample" );
+    hipLaunchKernelGGL( k_mesh_sample, dim3( blocks_for( count, MESH_BLOCK ) ), dim3( MESH_BLOCK ), 0, st, A );
+  }
+  RS_TRY( hipGetLastError(), "resample: launch" );
   return RS_HIP_OK;
 }
 
@@ -237,18 +215,18 @@ int rs_hip_uniform_resample( const float* pos, const float* nor, const float* co
                              float* out_pos, float* out_nor, float* out_col, float* out_radii,
                              int32_t* out_class, int32_t* out_instance, int32_t* out_face )
 {
-  if( !pos || !out_pos ) return mesh_fail( RS_HIP_E_ARG, "uniform_resample: pos and out_pos are required" );
+  if( !pos || !out_pos ) return fail( RS_HIP_E_ARG, "uniform_resample: pos and out_pos are required" );
   // the plan alone first: a window is judged against n_samples before anything is uploaded
   int64_t n_samples = 0;
   {
     char err[256] = "";
     const int rc = mesh::plan( pos, n_vertices, faces, n_faces, &n_samples, nullptr, nullptr, nullptr, err, sizeof(err) );
-    if( rc ) return mesh_fail( rc, err );
+    if( rc ) return fail( rc, err );
   }
   if( first < 0 || count < 0 || first > n_samples || count > n_samples - first )
   {
     char msg[160]; snprintf( msg, sizeof(msg), "uniform_resample: the window [%lld, %lld + %lld) is not inside the %lld samples", (long long)first, (long long)first, (long long)count, (long long)n_samples );
-    return mesh_fail( RS_HIP_E_ARG, msg );
+    return fail( RS_HIP_E_ARG, msg );
   }
   if( count == 0 ) return RS_HIP_OK;
   const MeshIn M{ pos, nor, col, radii, class_ids, instance_ids, n_vertices, faces, n_faces };
@@ -264,22 +242,22 @@ int rs_hip_uniform_resample( const float* pos, const float* nor, const float* co
   {
     dev[a] = nullptr;
     if( !host[a] ) continue;
-    MESH_TRY( W.out[a].ensure( (size_t)count * words[a] * 4 ), "resample: buffers" );
+    RS_TRY( W.out[a].ensure( (size_t)count * words[a] * 4 ), "resample: buffers" );
     dev[a] = W.out[a].p;
   }
   A.out_pos = (float*)dev[0]; A.out_nor = (float*)dev[1]; A.out_col = (float*)dev[2]; A.out_radii = (float*)dev[3];
   A.out_class = (int32_t*)dev[4]; A.out_instance = (int32_t*)dev[5]; A.out_face = (int32_t*)dev[6];
   rc = mesh_launch( A, first, count, st ); if( rc ) return rc;
   for( int a = 0; a < 7; ++a )
-    if( host[a] ) MESH_TRY( hipMemcpyAsync( host[a], dev[a], (size_t)count * words[a] * 4, hipMemcpyDeviceToHost, st ), "resample: download" );
-  MESH_TRY( hipStreamSynchronize( st ), "resample: kernel" );
+    if( host[a] ) RS_TRY( hipMemcpyAsync( host[a], dev[a], (size_t)count * words[a] * 4, hipMemcpyDeviceToHost, st ), "resample: download" );
+  RS_TRY( hipStreamSynchronize( st ), "resample: kernel" );
   return RS_HIP_OK;
 }
 
 rs_hip_cloud_t* rs_hip_cloud_create_resampled( const float* pos, const float* nor, int64_t n_vertices,
                                                const int32_t* faces, int64_t n_faces, float cell_size, int64_t* n_samples )
 {
-  if( !pos ) { mesh_fail( RS_HIP_E_ARG, "cloud_create_resampled: pos is required" ); return nullptr; }
+  if( !pos ) { fail( RS_HIP_E_ARG, "cloud_create_resampled: pos is required" ); return nullptr; }
   const MeshIn M{ pos, nor, nullptr, nullptr, nullptr, nullptr, n_vertices, faces, n_faces };
   MeshSampleArgs A; hipStream_t st = nullptr; int64_t count = 0;
   if( mesh_prepare( M, &count, A, &st ) ) return nullptr;

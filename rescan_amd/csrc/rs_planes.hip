@@ -23,8 +23,7 @@
 //   k_plane_gather_flags + scan + k_plane_scatter   one flag per (model, point), one exclusive scan over all of them, index and
 //                        offsets from the ranks: stable, so each model's indices increase.
 //   k_plane_relabel      one lane per point, the models in a loop: the relabel's gather and its writes fused, no index list.
-#include "../../include/rescan_hip.h"
-#include "rs_device.h"
+#include "rs_host.h"
 #include "rs_planes.h"
 
 #include <algorithm>
@@ -216,34 +215,9 @@ using namespace rs;
 
 namespace {
 
-struct PlaneBuf
-{
-  void* p = nullptr; size_t cap = 0;
-  hipError_t ensure( size_t bytes )
-  {
-    if( bytes <= cap ) return hipSuccess;
-    if( p ) { hipError_t e = hipFree( p ); if( e != hipSuccess ) return e; p = nullptr; cap = 0; }
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc( &p, want );
-    if( e == hipSuccess ) cap = want;
-    return e;
-  }
-  template <class T> T* as() { return (T*)p; }
-};
-struct PlaneWorkspace { PlaneBuf pts, pos3, floor_mask, wall_mask, flags, rank, tmp, cand, hyp, valid, counts, best, models, index, cls, inst; };
+struct PlaneWorkspace { Buf pts, pos3, floor_mask, wall_mask, flags, rank, tmp, cand, hyp, valid, counts, best, models, index, cls, inst; };
 thread_local PlaneWorkspace g_plane_ws;
 int32_t g_plane_form = 0;
-
-int plane_fail( int rc, const char* what, hipError_t e = hipSuccess )
-{
-  char msg[384];
-  snprintf( msg, sizeof(msg), "%s%s%s", what, e != hipSuccess ? ": " : "", e != hipSuccess ? hipGetErrorString( e ) : "" );
-  api_set_err( msg );
-  return rc;
-}
-#define PLANE_TRY( expr, what ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) return plane_fail( RS_HIP_E_RUNTIME, what, e_ ); } while( 0 )
-
-unsigned plane_blocks( long long n ) { return (unsigned)std::max<long long>( 1, ( n + PLANE_BLOCK - 1 ) / PLANE_BLOCK ); }
 
 // The votes of n_hyp hypotheses (host arrays) over the points of W.pts that `mask` (device, n >= 1 bytes) keeps: compaction, votes
 // and, where best is asked for, the best; counts land in W.counts, {index, count} in W.best.  *n_cand: the candidates.
@@ -253,10 +227,10 @@ int plane_round_device( int n, const uint8_t* d_mask, const float* center, const
   PlaneWorkspace& W = g_plane_ws;
   const size_t n1 = (size_t)n + 1, hh = (size_t)std::max( n_hyp, 1 );
   const size_t tmp_bytes = build_scan_temp_bytes( n1 );
-  PLANE_TRY( W.flags.ensure( n1 * 4 ), "planes: buffers" ); PLANE_TRY( W.rank.ensure( n1 * 4 ), "planes: buffers" );
-  PLANE_TRY( W.tmp.ensure( tmp_bytes + 256 ), "planes: buffers" ); PLANE_TRY( W.cand.ensure( (size_t)n * 16 ), "planes: buffers" );
-  PLANE_TRY( W.hyp.ensure( hh * 32 ), "planes: buffers" ); PLANE_TRY( W.valid.ensure( hh ), "planes: buffers" );
-  PLANE_TRY( W.counts.ensure( hh * 4 ), "planes: buffers" ); PLANE_TRY( W.best.ensure( 8 ), "planes: buffers" );
+  RS_TRY( W.flags.ensure( n1 * 4 ), "planes: buffers" ); RS_TRY( W.rank.ensure( n1 * 4 ), "planes: buffers" );
+  RS_TRY( W.tmp.ensure( tmp_bytes + 256 ), "planes: buffers" ); RS_TRY( W.cand.ensure( (size_t)n * 16 ), "planes: buffers" );
+  RS_TRY( W.hyp.ensure( hh * 32 ), "planes: buffers" ); RS_TRY( W.valid.ensure( hh ), "planes: buffers" );
+  RS_TRY( W.counts.ensure( hh * 4 ), "planes: buffers" ); RS_TRY( W.best.ensure( 8 ), "planes: buffers" );
   std::vector<float> packed( hh * 8, 0.0f );
   for( int h = 0; h < n_hyp; ++h )
   {
@@ -264,39 +238,39 @@ int plane_round_device( int n, const uint8_t* d_mask, const float* center, const
     std::memcpy( &packed[8 * (size_t)h + 4], normal + 3 * (size_t)h, 12 );
   }
   // (pageable memory: the copies have left the host arrays when the calls return)
-  PLANE_TRY( hipMemcpyAsync( W.hyp.p, packed.data(), hh * 32, hipMemcpyHostToDevice, st ), "planes: upload" );
-  if( valid && n_hyp > 0 ) PLANE_TRY( hipMemcpyAsync( W.valid.p, valid, (size_t)n_hyp, hipMemcpyHostToDevice, st ), "planes: upload" );
-  PLANE_TRY( hipMemsetAsync( W.counts.p, 0, hh * 4, st ), "planes: clear" );
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_plane_flags, dim3( plane_blocks( (long long)n1 ) ), dim3( PLANE_BLOCK ), 0, st, d_mask, n, W.flags.as<uint32_t>() );
-  const int scan_rc = build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st );
-  if( !scan_rc )
-    hipLaunchKernelGGL( k_plane_compact, dim3( plane_blocks( n ) ), dim3( PLANE_BLOCK ), 0, st, W.pts.as<float4>(), W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n, W.cand.as<float4>() );
-  api_prof_end( "plane_compact", ev );
-  if( scan_rc ) return plane_fail( RS_HIP_E_RUNTIME, "planes: device scan failed" );
-  PLANE_TRY( hipGetLastError(), "planes: compaction launch" );
-  uint32_t got = 0;
-  PLANE_TRY( hipMemcpyAsync( &got, W.rank.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ), "planes: download" );
-  PLANE_TRY( hipStreamSynchronize( st ), "planes: compaction" );
-  *n_cand = (int64_t)got;
-  ev = api_prof_begin();
-  if( got > 0 && n_hyp > 0 )
+  RS_TRY( hipMemcpyAsync( W.hyp.p, packed.data(), hh * 32, hipMemcpyHostToDevice, st ), "planes: upload" );
+  if( valid && n_hyp > 0 ) RS_TRY( hipMemcpyAsync( W.valid.p, valid, (size_t)n_hyp, hipMemcpyHostToDevice, st ), "planes: upload" );
+  RS_TRY( hipMemsetAsync( W.counts.p, 0, hh * 4, st ), "planes: clear" );
   {
-    const dim3 grid( plane_blocks( n_hyp ), ( got + PLANE_TILE - 1 ) / PLANE_TILE );
-    const uint8_t* d_valid = valid ? W.valid.as<uint8_t>() : nullptr;
-    if( g_plane_form == 0 )
-      hipLaunchKernelGGL( k_plane_votes<true>, grid, dim3( PLANE_BLOCK ), 0, st, W.cand.as<float4>(), (int)got, W.hyp.as<float4>(), d_valid, n_hyp, dist_threshold, W.counts.as<int32_t>() );
-    else
-      hipLaunchKernelGGL( k_plane_votes<false>, grid, dim3( PLANE_BLOCK ), 0, st, W.cand.as<float4>(), (int)got, W.hyp.as<float4>(), d_valid, n_hyp, dist_threshold, W.counts.as<int32_t>() );
+    ProfSpan span( "plane_compact" );
+    hipLaunchKernelGGL( k_plane_flags, dim3( blocks_for( (long long)n1, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, d_mask, n, W.flags.as<uint32_t>() );
+    if( build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st ) )
+      return fail( RS_HIP_E_RUNTIME, "planes: device scan failed" );
+    hipLaunchKernelGGL( k_plane_compact, dim3( blocks_for( n, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, W.pts.as<float4>(), W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n, W.cand.as<float4>() );
   }
-  api_prof_end( "plane_votes", ev );
+  RS_TRY( hipGetLastError(), "planes: compaction launch" );
+  uint32_t got = 0;
+  RS_TRY( hipMemcpyAsync( &got, W.rank.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st ), "planes: download" );
+  RS_TRY( hipStreamSynchronize( st ), "planes: compaction" );
+  *n_cand = (int64_t)got;
+  {
+    ProfSpan span( "plane_votes" );
+    if( got > 0 && n_hyp > 0 )
+    {
+      const dim3 grid( blocks_for( n_hyp, PLANE_BLOCK ), ( got + PLANE_TILE - 1 ) / PLANE_TILE );
+      const uint8_t* d_valid = valid ? W.valid.as<uint8_t>() : nullptr;
+      if( g_plane_form == 0 )
+        hipLaunchKernelGGL( k_plane_votes<true>, grid, dim3( PLANE_BLOCK ), 0, st, W.cand.as<float4>(), (int)got, W.hyp.as<float4>(), d_valid, n_hyp, dist_threshold, W.counts.as<int32_t>() );
+      else
+        hipLaunchKernelGGL( k_plane_votes<false>, grid, dim3( PLANE_BLOCK ), 0, st, W.cand.as<float4>(), (int)got, W.hyp.as<float4>(), d_valid, n_hyp, dist_threshold, W.counts.as<int32_t>() );
+    }
+  }
   if( with_best )
   {
-    ev = api_prof_begin();
+    ProfSpan span( "plane_best" );
     hipLaunchKernelGGL( k_plane_best, dim3( 1 ), dim3( PLANE_BLOCK ), 0, st, W.counts.as<int32_t>(), n_hyp, W.best.as<int32_t>() );
-    api_prof_end( "plane_best", ev );
   }
-  PLANE_TRY( hipGetLastError(), "planes: votes launch" );
+  RS_TRY( hipGetLastError(), "planes: votes launch" );
   return RS_HIP_OK;
 }
 
@@ -315,9 +289,9 @@ int plane_upload_models( const float* centers, const float* normals, const float
     G.up_dot = up_dot ? up_dot[m] : 0.0f;
     G.valid = valid ? ( valid[m] ? 1 : 0 ) : 1;
   }
-  PLANE_TRY( W.models.ensure( M.size() * sizeof(PlaneGatherModel) ), "planes: buffers" );
-  PLANE_TRY( hipMemcpyAsync( W.models.p, M.data(), M.size() * sizeof(PlaneGatherModel), hipMemcpyHostToDevice, st ), "planes: upload" );
-  PLANE_TRY( hipStreamSynchronize( st ), "planes: upload" );     // M leaves scope
+  RS_TRY( W.models.ensure( M.size() * sizeof(PlaneGatherModel) ), "planes: buffers" );
+  RS_TRY( hipMemcpyAsync( W.models.p, M.data(), M.size() * sizeof(PlaneGatherModel), hipMemcpyHostToDevice, st ), "planes: upload" );
+  RS_TRY( hipStreamSynchronize( st ), "planes: upload" );     // M leaves scope
   return RS_HIP_OK;
 }
 
@@ -345,22 +319,22 @@ int rs_hip_plane_votes( const float* pos, int64_t n, const uint8_t* active, cons
                         const uint8_t* valid, int32_t n_hyp, float dist_threshold, int32_t* counts )
 {
   if( n < 0 || n_hyp < 0 || ( n > 0 && ( !pos || !active ) ) || ( n_hyp > 0 && ( !center || !normal || !counts ) ) )
-    return plane_fail( RS_HIP_E_ARG, "plane_votes: null arrays or a negative count" );
-  if( n > planes::MAX_POINTS ) return plane_fail( RS_HIP_E_CAPACITY, "plane_votes: more than 2^24 points" );
+    return fail( RS_HIP_E_ARG, "plane_votes: null arrays or a negative count" );
+  if( n > planes::MAX_POINTS ) return fail( RS_HIP_E_CAPACITY, "plane_votes: more than 2^24 points" );
   if( n_hyp == 0 ) return RS_HIP_OK;
   if( n == 0 ) { std::memset( counts, 0, (size_t)n_hyp * 4 ); return RS_HIP_OK; }
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   PlaneWorkspace& W = g_plane_ws;
-  PLANE_TRY( W.pos3.ensure( (size_t)n * 12 ), "plane_votes: buffers" ); PLANE_TRY( W.pts.ensure( (size_t)n * 16 ), "plane_votes: buffers" );
-  PLANE_TRY( W.wall_mask.ensure( (size_t)n ), "plane_votes: buffers" );
-  PLANE_TRY( hipMemcpyAsync( W.pos3.p, pos, (size_t)n * 12, hipMemcpyHostToDevice, st ), "plane_votes: upload" );
-  PLANE_TRY( hipMemcpyAsync( W.wall_mask.p, active, (size_t)n, hipMemcpyHostToDevice, st ), "plane_votes: upload" );
-  hipLaunchKernelGGL( k_plane_pack, dim3( plane_blocks( n ) ), dim3( PLANE_BLOCK ), 0, st, W.pos3.as<float>(), (int)n, W.pts.as<float4>() );
+  RS_TRY( W.pos3.ensure( (size_t)n * 12 ), "plane_votes: buffers" ); RS_TRY( W.pts.ensure( (size_t)n * 16 ), "plane_votes: buffers" );
+  RS_TRY( W.wall_mask.ensure( (size_t)n ), "plane_votes: buffers" );
+  RS_TRY( hipMemcpyAsync( W.pos3.p, pos, (size_t)n * 12, hipMemcpyHostToDevice, st ), "plane_votes: upload" );
+  RS_TRY( hipMemcpyAsync( W.wall_mask.p, active, (size_t)n, hipMemcpyHostToDevice, st ), "plane_votes: upload" );
+  hipLaunchKernelGGL( k_plane_pack, dim3( blocks_for( n, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, W.pos3.as<float>(), (int)n, W.pts.as<float4>() );
   int64_t n_cand = 0;
   rc = plane_round_device( (int)n, W.wall_mask.as<uint8_t>(), center, normal, valid, n_hyp, dist_threshold, false, &n_cand, st ); if( rc ) return rc;
-  PLANE_TRY( hipMemcpyAsync( counts, W.counts.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, st ), "plane_votes: download" );
-  PLANE_TRY( hipStreamSynchronize( st ), "plane_votes: kernels" );
+  RS_TRY( hipMemcpyAsync( counts, W.counts.p, (size_t)n_hyp * 4, hipMemcpyDeviceToHost, st ), "plane_votes: download" );
+  RS_TRY( hipStreamSynchronize( st ), "plane_votes: kernels" );
   return RS_HIP_OK;
 }
 
@@ -370,26 +344,26 @@ int rs_hip_detect_planes( const rs_hip_cloud_t* cloud, float dot_threshold, floa
 {
   if( !cloud || !n_floors || !n_walls || !n_models || capacity < 0 || floor_iters < 0 || wall_iters < 0 || count_threshold < 0 ||
       ( capacity > 0 && ( !centers || !normals || !n_inliers ) ) )
-    return plane_fail( RS_HIP_E_ARG, "detect_planes: null arrays or a negative count" );
+    return fail( RS_HIP_E_ARG, "detect_planes: null arrays or a negative count" );
   if( trace && ( trace->capacity_rounds < 0 || trace->max_iters < std::max( floor_iters, wall_iters ) ) )
-    return plane_fail( RS_HIP_E_ARG, "detect_planes: the trace's max_iters is below an iteration count, or its capacity is negative" );
+    return fail( RS_HIP_E_ARG, "detect_planes: the trace's max_iters is below an iteration count, or its capacity is negative" );
   const CloudPoints S = api_cloud_points( cloud );
-  if( !S.qnor ) return plane_fail( RS_HIP_E_ARG, "detect_planes: the cloud needs normals" );
-  if( S.n > planes::MAX_POINTS ) return plane_fail( RS_HIP_E_CAPACITY, "detect_planes: more than 2^24 points: beyond it the reference's (float)n is inexact" );
-  if( S.n <= 0 ) return plane_fail( RS_HIP_E_ARG, "detect_planes: an empty cloud has no candidates: the reference's pdf would stay uninitialised" );
+  if( !S.qnor ) return fail( RS_HIP_E_ARG, "detect_planes: the cloud needs normals" );
+  if( S.n > planes::MAX_POINTS ) return fail( RS_HIP_E_CAPACITY, "detect_planes: more than 2^24 points: beyond it the reference's (float)n is inexact" );
+  if( S.n <= 0 ) return fail( RS_HIP_E_ARG, "detect_planes: an empty cloud has no candidates: the reference's pdf would stay uninitialised" );
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   PlaneWorkspace& W = g_plane_ws;
   const int n = S.n;
-  PLANE_TRY( W.pts.ensure( (size_t)n * 16 ), "detect_planes: buffers" );
-  PLANE_TRY( W.floor_mask.ensure( (size_t)n ), "detect_planes: buffers" ); PLANE_TRY( W.wall_mask.ensure( (size_t)n ), "detect_planes: buffers" );
-  hipLaunchKernelGGL( k_plane_candidates, dim3( plane_blocks( n ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, n, dot_threshold,
+  RS_TRY( W.pts.ensure( (size_t)n * 16 ), "detect_planes: buffers" );
+  RS_TRY( W.floor_mask.ensure( (size_t)n ), "detect_planes: buffers" ); RS_TRY( W.wall_mask.ensure( (size_t)n ), "detect_planes: buffers" );
+  hipLaunchKernelGGL( k_plane_candidates, dim3( blocks_for( n, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, n, dot_threshold,
                       W.pts.as<float4>(), W.floor_mask.as<uint8_t>(), W.wall_mask.as<uint8_t>() );
-  PLANE_TRY( hipGetLastError(), "detect_planes: candidates launch" );
+  RS_TRY( hipGetLastError(), "detect_planes: candidates launch" );
   // the planner reads positions on the host: three of them per hypothesis
   std::vector<float4> pts4( (size_t)n );
-  PLANE_TRY( hipMemcpyAsync( pts4.data(), W.pts.p, (size_t)n * 16, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
-  PLANE_TRY( hipStreamSynchronize( st ), "detect_planes: candidates" );
+  RS_TRY( hipMemcpyAsync( pts4.data(), W.pts.p, (size_t)n * 16, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
+  RS_TRY( hipStreamSynchronize( st ), "detect_planes: candidates" );
   std::vector<float> pos( 3 * (size_t)n );
   for( int i = 0; i < n; ++i ) { pos[3 * (size_t)i] = pts4[(size_t)i].x; pos[3 * (size_t)i + 1] = pts4[(size_t)i].y; pos[3 * (size_t)i + 2] = pts4[(size_t)i].z; }
   std::vector<float4>().swap( pts4 );
@@ -405,21 +379,21 @@ int rs_hip_detect_planes( const rs_hip_cloud_t* cloud, float dot_threshold, floa
   auto run_round = [&]( uint8_t* d_mask, int n_iter, int distinct, int32_t* best_idx, int32_t* best_count ) -> int
   {
     char err[256] = "";
-    PLANE_TRY( hipMemcpyAsync( mask.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
-    PLANE_TRY( hipStreamSynchronize( st ), "detect_planes: mask" );
+    RS_TRY( hipMemcpyAsync( mask.data(), d_mask, (size_t)n, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
+    RS_TRY( hipStreamSynchronize( st ), "detect_planes: mask" );
     idx.assign( 3 * (size_t)n_iter, 0 ); hc.assign( 3 * (size_t)n_iter, 0.0f ); hn.assign( 3 * (size_t)n_iter, 0.0f ); valid.assign( (size_t)n_iter, 1 );
     if( int prc = planes::hypotheses( pos.data(), n, mask.data(), n_iter, distinct, planes::SEED, idx.data(), hc.data(), hn.data(), err, sizeof(err) ) )
-      return plane_fail( prc, err );
+      return fail( prc, err );
     if( distinct )
       for( int h = 0; h < n_iter; ++h ) valid[(size_t)h] = planes::abs_ref( planes::up_dot( &hn[3 * (size_t)h] ) ) < wall_limit ? 1 : 0;
     int64_t n_cand = 0;
     if( int drc = plane_round_device( n, d_mask, hc.data(), hn.data(), valid.data(), n_iter, dist_threshold, true, &n_cand, st ) ) return drc;
     int32_t best[2] = { -1, 0 };
-    PLANE_TRY( hipMemcpyAsync( best, W.best.p, 8, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
+    RS_TRY( hipMemcpyAsync( best, W.best.p, 8, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
     const bool rec = trace && round < trace->capacity_rounds;
     if( rec && trace->counts && n_iter > 0 )
-      PLANE_TRY( hipMemcpyAsync( trace->counts + (size_t)round * trace->max_iters, W.counts.p, (size_t)n_iter * 4, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
-    PLANE_TRY( hipStreamSynchronize( st ), "detect_planes: votes" );
+      RS_TRY( hipMemcpyAsync( trace->counts + (size_t)round * trace->max_iters, W.counts.p, (size_t)n_iter * 4, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
+    RS_TRY( hipStreamSynchronize( st ), "detect_planes: votes" );
     if( n_iter == 0 ) { best[0] = -1; best[1] = 0; }
     *best_idx = best[0]; *best_count = best[1];
     if( rec )
@@ -435,8 +409,8 @@ int rs_hip_detect_planes( const rs_hip_cloud_t* cloud, float dot_threshold, floa
   auto record_mask_after = [&]( const uint8_t* d_mask ) -> int
   {
     if( !( trace && round < trace->capacity_rounds && trace->mask_after ) ) return RS_HIP_OK;
-    PLANE_TRY( hipMemcpyAsync( trace->mask_after + (size_t)round * n, d_mask, (size_t)n, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
-    PLANE_TRY( hipStreamSynchronize( st ), "detect_planes: mask" );
+    RS_TRY( hipMemcpyAsync( trace->mask_after + (size_t)round * n, d_mask, (size_t)n, hipMemcpyDeviceToHost, st ), "detect_planes: download" );
+    RS_TRY( hipStreamSynchronize( st ), "detect_planes: mask" );
     return RS_HIP_OK;
   };
 
@@ -465,15 +439,15 @@ int rs_hip_detect_planes( const rs_hip_cloud_t* cloud, float dot_threshold, floa
     }
     // :192: with the round's best, or — nothing detected — the model the last round left there
     PlaneModel R; std::memcpy( R.c, best_wall.c, 12 ); std::memcpy( R.n, best_wall.n, 12 );
-    hipLaunchKernelGGL( k_plane_remove, dim3( plane_blocks( n ) ), dim3( PLANE_BLOCK ), 0, st, W.pts.as<float4>(), n, R, dist_threshold, W.wall_mask.as<uint8_t>() );
-    PLANE_TRY( hipGetLastError(), "detect_planes: remove launch" );
+    hipLaunchKernelGGL( k_plane_remove, dim3( blocks_for( n, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, W.pts.as<float4>(), n, R, dist_threshold, W.wall_mask.as<uint8_t>() );
+    RS_TRY( hipGetLastError(), "detect_planes: remove launch" );
     rc = record_mask_after( W.wall_mask.as<uint8_t>() ); if( rc ) return rc;
     ++round; ++walls;
   } while( best_wall.count > count_threshold );
-  if( models.empty() ) return plane_fail( RS_HIP_E_ARG, "detect_planes: no floor and no wall: the reference would pop an empty model array" );
+  if( models.empty() ) return fail( RS_HIP_E_ARG, "detect_planes: no floor and no wall: the reference would pop an empty model array" );
   models.pop_back();                                                      // :197
   --walls;
-  if( (int64_t)models.size() > capacity ) return plane_fail( RS_HIP_E_CAPACITY, "detect_planes: more models than the caller's capacity" );
+  if( (int64_t)models.size() > capacity ) return fail( RS_HIP_E_CAPACITY, "detect_planes: more models than the caller's capacity" );
   for( size_t m = 0; m < models.size(); ++m )
   {
     std::memcpy( centers + 3 * m, models[m].c, 12 ); std::memcpy( normals + 3 * m, models[m].n, 12 ); n_inliers[m] = models[m].count;
@@ -490,11 +464,11 @@ int rs_hip_gather_plane_inliers( const rs_hip_cloud_t* cloud, const float* cente
 {
   if( !cloud || !offsets || n_models < 0 || capacity < 0 || ( capacity > 0 && !index ) ||
       ( n_models > 0 && ( !centers || !normals || ( check_validity && !valid ) || ( check_extends && ( !axes || !extends ) ) ) ) )
-    return plane_fail( RS_HIP_E_ARG, "gather_plane_inliers: null arrays or a negative count" );
+    return fail( RS_HIP_E_ARG, "gather_plane_inliers: null arrays or a negative count" );
   const CloudPoints S = api_cloud_points( cloud );
-  if( !S.qnor ) return plane_fail( RS_HIP_E_ARG, "gather_plane_inliers: the cloud needs normals" );
+  if( !S.qnor ) return fail( RS_HIP_E_ARG, "gather_plane_inliers: the cloud needs normals" );
   const long long total = (long long)n_models * std::max( S.n, 0 );
-  if( total > 2147483646ll ) return plane_fail( RS_HIP_E_CAPACITY, "gather_plane_inliers: models x points exceed what one scan of 2^31 flags holds" );
+  if( total > 2147483646ll ) return fail( RS_HIP_E_CAPACITY, "gather_plane_inliers: models x points exceed what one scan of 2^31 flags holds" );
   if( total == 0 ) { for( int m = 0; m <= n_models; ++m ) offsets[m] = 0; return RS_HIP_OK; }
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
@@ -502,30 +476,32 @@ int rs_hip_gather_plane_inliers( const rs_hip_cloud_t* cloud, const float* cente
   rc = plane_upload_models( centers, normals, axes, extends, check_validity ? valid : nullptr, nullptr, n_models, check_extends != 0, st ); if( rc ) return rc;
   const size_t n1 = (size_t)total + 1;
   const size_t tmp_bytes = build_scan_temp_bytes( n1 );
-  PLANE_TRY( W.flags.ensure( n1 * 4 ), "gather_plane_inliers: buffers" ); PLANE_TRY( W.rank.ensure( n1 * 4 ), "gather_plane_inliers: buffers" );
-  PLANE_TRY( W.tmp.ensure( tmp_bytes + 256 ), "gather_plane_inliers: buffers" );
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_plane_gather_flags, dim3( plane_blocks( (long long)n1 ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, S.n,
-                      W.models.as<PlaneGatherModel>(), n_models, dot_threshold, dist_threshold, check_validity, check_extends, W.flags.as<uint32_t>() );
-  const int scan_rc = build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st );
-  api_prof_end( "plane_gather_flags", ev );
-  if( scan_rc ) return plane_fail( RS_HIP_E_RUNTIME, "gather_plane_inliers: device scan failed" );
-  PLANE_TRY( hipGetLastError(), "gather_plane_inliers: flags launch" );
+  RS_TRY( W.flags.ensure( n1 * 4 ), "gather_plane_inliers: buffers" ); RS_TRY( W.rank.ensure( n1 * 4 ), "gather_plane_inliers: buffers" );
+  RS_TRY( W.tmp.ensure( tmp_bytes + 256 ), "gather_plane_inliers: buffers" );
+  {
+    ProfSpan span( "plane_gather_flags" );
+    hipLaunchKernelGGL( k_plane_gather_flags, dim3( blocks_for( (long long)n1, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, S.n,
+                        W.models.as<PlaneGatherModel>(), n_models, dot_threshold, dist_threshold, check_validity, check_extends, W.flags.as<uint32_t>() );
+    if( build_exclusive_scan( W.tmp.p, tmp_bytes, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), n1, st ) )
+      return fail( RS_HIP_E_RUNTIME, "gather_plane_inliers: device scan failed" );
+  }
+  RS_TRY( hipGetLastError(), "gather_plane_inliers: flags launch" );
   std::vector<uint32_t> off( (size_t)n_models + 1 );
   for( int m = 0; m <= n_models; ++m )
-    PLANE_TRY( hipMemcpyAsync( &off[(size_t)m], W.rank.as<uint32_t>() + (size_t)m * S.n, 4, hipMemcpyDeviceToHost, st ), "gather_plane_inliers: download" );
-  PLANE_TRY( hipStreamSynchronize( st ), "gather_plane_inliers: flags" );
+    RS_TRY( hipMemcpyAsync( &off[(size_t)m], W.rank.as<uint32_t>() + (size_t)m * S.n, 4, hipMemcpyDeviceToHost, st ), "gather_plane_inliers: download" );
+  RS_TRY( hipStreamSynchronize( st ), "gather_plane_inliers: flags" );
   const uint32_t count = off[(size_t)n_models];
-  if( (int64_t)count > capacity ) return plane_fail( RS_HIP_E_CAPACITY, "gather_plane_inliers: more inliers than the caller's capacity" );
+  if( (int64_t)count > capacity ) return fail( RS_HIP_E_CAPACITY, "gather_plane_inliers: more inliers than the caller's capacity" );
   if( count > 0 )
   {
-    PLANE_TRY( W.index.ensure( (size_t)count * 4 ), "gather_plane_inliers: buffers" );
-    ev = api_prof_begin();
-    hipLaunchKernelGGL( k_plane_scatter, dim3( plane_blocks( total ) ), dim3( PLANE_BLOCK ), 0, st, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), S.n, total, W.index.as<int32_t>() );
-    api_prof_end( "plane_scatter", ev );
-    PLANE_TRY( hipGetLastError(), "gather_plane_inliers: scatter launch" );
-    PLANE_TRY( hipMemcpyAsync( index, W.index.p, (size_t)count * 4, hipMemcpyDeviceToHost, st ), "gather_plane_inliers: download" );
-    PLANE_TRY( hipStreamSynchronize( st ), "gather_plane_inliers: scatter" );
+    RS_TRY( W.index.ensure( (size_t)count * 4 ), "gather_plane_inliers: buffers" );
+    {
+      ProfSpan span( "plane_scatter" );
+      hipLaunchKernelGGL( k_plane_scatter, dim3( blocks_for( total, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, W.flags.as<uint32_t>(), W.rank.as<uint32_t>(), S.n, total, W.index.as<int32_t>() );
+    }
+    RS_TRY( hipGetLastError(), "gather_plane_inliers: scatter launch" );
+    RS_TRY( hipMemcpyAsync( index, W.index.p, (size_t)count * 4, hipMemcpyDeviceToHost, st ), "gather_plane_inliers: download" );
+    RS_TRY( hipStreamSynchronize( st ), "gather_plane_inliers: scatter" );
   }
   for( int m = 0; m <= n_models; ++m ) offsets[m] = (int64_t)off[(size_t)m];
   return RS_HIP_OK;
@@ -536,29 +512,30 @@ int rs_hip_relabel_walls_and_floors( const rs_hip_cloud_t* cloud, const float* c
                                      int32_t floor_idx, int32_t wall_idx, int32_t unlabelled_idx, int32_t* class_ids, int32_t* instance_ids )
 {
   if( !cloud || n_models < 0 || ( n_models > 0 && ( !centers || !normals || !axes || !extends || !valid || !normal_up_dot ) ) )
-    return plane_fail( RS_HIP_E_ARG, "relabel_walls_and_floors: null arrays or a negative count" );
+    return fail( RS_HIP_E_ARG, "relabel_walls_and_floors: null arrays or a negative count" );
   const CloudPoints S = api_cloud_points( cloud );
-  if( !S.qnor ) return plane_fail( RS_HIP_E_ARG, "relabel_walls_and_floors: the cloud needs normals" );
-  if( S.n > 0 && ( !class_ids || !instance_ids ) ) return plane_fail( RS_HIP_E_ARG, "relabel_walls_and_floors: the class and instance ids are required" );
+  if( !S.qnor ) return fail( RS_HIP_E_ARG, "relabel_walls_and_floors: the cloud needs normals" );
+  if( S.n > 0 && ( !class_ids || !instance_ids ) ) return fail( RS_HIP_E_ARG, "relabel_walls_and_floors: the class and instance ids are required" );
   if( S.n <= 0 || n_models == 0 ) return RS_HIP_OK;
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
   PlaneWorkspace& W = g_plane_ws;
   rc = plane_upload_models( centers, normals, axes, extends, valid, normal_up_dot, n_models, true, st ); if( rc ) return rc;
   const size_t bytes = (size_t)S.n * 4;
-  PLANE_TRY( W.cls.ensure( bytes ), "relabel_walls_and_floors: buffers" ); PLANE_TRY( W.inst.ensure( bytes ), "relabel_walls_and_floors: buffers" );
-  PLANE_TRY( hipMemcpyAsync( W.cls.p, class_ids, bytes, hipMemcpyHostToDevice, st ), "relabel_walls_and_floors: upload" );
-  PLANE_TRY( hipMemcpyAsync( W.inst.p, instance_ids, bytes, hipMemcpyHostToDevice, st ), "relabel_walls_and_floors: upload" );
-  void* ev = api_prof_begin();
-  hipLaunchKernelGGL( k_plane_relabel, dim3( plane_blocks( S.n ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, S.n,
-                      W.models.as<PlaneGatherModel>(), n_models, floor_idx, wall_idx, unlabelled_idx, W.cls.as<int32_t>(), W.inst.as<int32_t>() );
-  api_prof_end( "plane_relabel", ev );
-  PLANE_TRY( hipGetLastError(), "relabel_walls_and_floors: launch" );
+  RS_TRY( W.cls.ensure( bytes ), "relabel_walls_and_floors: buffers" ); RS_TRY( W.inst.ensure( bytes ), "relabel_walls_and_floors: buffers" );
+  RS_TRY( hipMemcpyAsync( W.cls.p, class_ids, bytes, hipMemcpyHostToDevice, st ), "relabel_walls_and_floors: upload" );
+  RS_TRY( hipMemcpyAsync( W.inst.p, instance_ids, bytes, hipMemcpyHostToDevice, st ), "relabel_walls_and_floors: upload" );
+  {
+    ProfSpan span( "plane_relabel" );
+    hipLaunchKernelGGL( k_plane_relabel, dim3( blocks_for( S.n, PLANE_BLOCK ) ), dim3( PLANE_BLOCK ), 0, st, S.qpos, S.qnor, S.by_orig, S.n,
+                        W.models.as<PlaneGatherModel>(), n_models, floor_idx, wall_idx, unlabelled_idx, W.cls.as<int32_t>(), W.inst.as<int32_t>() );
+  }
+  RS_TRY( hipGetLastError(), "relabel_walls_and_floors: launch" );
   // into scratch first: a failed download leaves the caller's arrays as they were
   std::vector<int32_t> cls( (size_t)S.n ), inst( (size_t)S.n );
-  PLANE_TRY( hipMemcpyAsync( cls.data(), W.cls.p, bytes, hipMemcpyDeviceToHost, st ), "relabel_walls_and_floors: download" );
-  PLANE_TRY( hipMemcpyAsync( inst.data(), W.inst.p, bytes, hipMemcpyDeviceToHost, st ), "relabel_walls_and_floors: download" );
-  PLANE_TRY( hipStreamSynchronize( st ), "relabel_walls_and_floors: kernel" );
+  RS_TRY( hipMemcpyAsync( cls.data(), W.cls.p, bytes, hipMemcpyDeviceToHost, st ), "relabel_walls_and_floors: download" );
+  RS_TRY( hipMemcpyAsync( inst.data(), W.inst.p, bytes, hipMemcpyDeviceToHost, st ), "relabel_walls_and_floors: download" );
+  RS_TRY( hipStreamSynchronize( st ), "relabel_walls_and_floors: kernel" );
   std::memcpy( class_ids, cls.data(), bytes ); std::memcpy( instance_ids, inst.data(), bytes );
   return RS_HIP_OK;
 }
