@@ -211,6 +211,12 @@ int64_t rs_hip_icp_stop_guard_redone( void );
  * reference's pose (<= 1.2e-6 without; with ONE chain iteration 1.1e-5: not shipped; profiles/r06/early_plain.txt).
  * Object-sized sources (up to 65536 points, whichever kernels run their chains) keep them in every iteration.  on < 0 only reads; returns the previous setting. */
 int32_t rs_hip_icp_early_plain( int32_t on );
+/* Plain iterations without records (round 10).  A plain step sums its moments in no particular order, so its search writes no 48-byte
+ * record per source point: it leaves matched slot, dist² and dot (12 B per point) and the moments are formed from those in the source's
+ * tile order, in fp64, by a fixed schedule (two runs give the same bits; against the step from records only the order of the fp64
+ * additions differs).  on = 1 (environment RS_HIP_PLAIN_RECORDS=1) brings the plain step from records back: for A/B runs and tests.
+ * on < 0 only reads; returns the previous setting.  The trace kind of both is RS_HIP_ICP_STEP_PLAIN. */
+int32_t rs_hip_icp_plain_from_records( int32_t on );
 float   rs_hip_icp_stop_guard( float guard );      /* sets the guard's width (0: off); < 0 only reads; returns the previous width */
 /* The sequential estimator (sources up to rs_hip_icp_reference_order_below) runs the reference's dist² statistics and its weighted
  * centroids in ONE pass, the 2.5 sigma cut of the weights (lib/rs/icp.h:396-401) taken at a guess of sigma; the pass stands when no

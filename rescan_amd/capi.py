@@ -56,6 +56,7 @@ SIGNATURES = {
     "rs_hip_icp_stop_guard_redone": (C.c_int64, []),
     "rs_hip_icp_stop_guard": (C.c_float, [C.c_float]),
     "rs_hip_icp_early_plain": (C.c_int32, [C.c_int32]),
+    "rs_hip_icp_plain_from_records": (C.c_int32, [C.c_int32]),
     "rs_hip_icp_replay_redone": (C.c_int32, []),
     "rs_hip_icp_faith_redone": (C.c_int32, []),
     "rs_hip_icp_faith_guess": (C.c_int32, [C.c_int32]),
@@ -627,6 +628,12 @@ def icp_stop_guard_redone():
 def icp_early_plain(on=-1):
     """Plain (chain-free) early iterations of the lane / grid chain estimators (default on); -1 only reads.  Returns the previous setting."""
     return int(load().rs_hip_icp_early_plain(int(on)))
+
+
+def icp_plain_from_records(on=-1):
+    """1: plain iterations read the searches' 48-byte records again (default 0: moments from the matches, no records written); -1 only reads.
+    Returns the previous setting."""
+    return int(load().rs_hip_icp_plain_from_records(int(on)))
 
 
 def icp_stop_guard(guard=-1.0):

@@ -155,11 +155,12 @@ void tr_clear_row( int g )
 // a call starts over for its problems 0 .. n-1: whatever an earlier attempt left in their rows goes
 void tr_clear( int n ) { if( g_tr.kinds ) for( int p = 0; p < n; ++p ) { const int g = tr_global( p ); if( g >= 0 ) tr_clear_row( g ); } }
 // The ICP loop's device-resident state, one 4-byte word array after the other (n = n_prob); array X starts at word ICP_ST_X * n:
-//   T1 16n | active n | T1_prev 16n | iters n | err n | prev_err n | queued n | ticket 2n
-// ticket[0..n) carries the stop guard's flags: [p] = 1 when a stop test of problem p came within L.stop_guard of its threshold
-// (k_icp_update); the other n words stay zero.
+//   T1 16n | active n | T1_prev 16n | iters n | err n | prev_err n | queued n | ticket n | failed n
+// ticket carries the stop guard's flags: [p] = 1 when a stop test of problem p came within L.stop_guard of its threshold
+// (k_icp_update); failed the grid chains' (ChainBufs::failed: [p] = 1 when a walk gave problem p up) — in the state block, so that the
+// give-up decision comes out of the copy and the synchronisation that end every call anyway.
 enum : size_t { ICP_ST_T1 = 0, ICP_ST_ACTIVE = 16, ICP_ST_T1_PREV = 17, ICP_ST_ITERS = 33, ICP_ST_ERR = 34, ICP_ST_PREV_ERR = 35,
-                ICP_ST_QUEUED = 36, ICP_ST_TICKET = 37, ICP_STATE_WORDS = 39 };
+                ICP_ST_QUEUED = 36, ICP_ST_TICKET = 37, ICP_ST_FAILED = 38, ICP_STATE_WORDS = 39 };
 // iteration i has just run for every problem with was_active[p]: its pose and error as the state holds them now (hS: the n-problem state)
 void tr_record( int n, int i, int kind, const float* hS, std::vector<char>& was_active )
 {
@@ -270,6 +271,13 @@ inline int icp_plain_iterations( int n_source, int max_iter, bool fixed_iters )
   if( fixed_iters ) return tail;
   return n_source > ICP_EXACT_PTS ? std::min( std::max( 0, 7 - keep ), tail ) : 0;
 }
+// PLAIN iterations without records (round 10).  A plain step is a sum in no particular order: nothing in it needs the 48-byte record a
+// search scatters to every source point's ORIGINAL index for the chains (icp_emit: pose and source reload, two gathers, three 16-byte
+// stores — 78 MB written per 1 M-point search, read back by k_chain_moments).  The search of a plain iteration therefore runs with
+// L.rec == null and k_plain_moments forms the moments from m_slot / m_d2 / m_dot in tile order (rs_icp_estimate.hip); the iterations that
+// keep the chains, or the RECORDS estimator's own, get their records from their own search as before.  RS_HIP_PLAIN_RECORDS=1 /
+// rs_hip_icp_plain_from_records( 1 ): the plain step from records again (A/B runs, tests).
+std::atomic<int> g_plain_records{ getenv( "RS_HIP_PLAIN_RECORDS" ) ? atoi( getenv( "RS_HIP_PLAIN_RECORDS" ) ) : 0 };
 std::mutex g_prof_mutex;
 struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> spans; int64_t launches = 0; double ms = 0.0; };
 std::map<std::string, ProfEntry> g_profmap;
@@ -1196,7 +1204,7 @@ int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
     CB.totals = RB.totals; CB.resolved = RB.redone;
     if( ( rc = g_ws.ch_done.ensure( np * 8 ) ) ) return rc;
     if( int rcf = icp_fill( g_ws.ch_done.p, 0, np * 8 ) ) return rcf;
-    CB.done = g_ws.ch_done.as<int>(); CB.failed = CB.done + n;
+    CB.done = g_ws.ch_done.as<int>(); CB.failed = (int*)( g_ws.state.as<float>() + np * ICP_ST_FAILED );      // (zero since icp_upload_state)
     if( getenv( "RS_HIP_CHAIN_DEBUG" ) )
     {
       if( ( rc = g_ws.ch_dbg.ensure( rows * ( 4 + 64 * 8 ) * 4 ) ) ) return rc;
@@ -1212,7 +1220,8 @@ int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
     }
     cx.L.rec = (float4*)g_ws.ch_rec.p;
     cx.L.n_mom_blocks = CB.n_blk * 4;              // k_chain_moments: one workgroup, one partial, per quarter block (1 024 source points)
-    if( ( rc = g_ws.mom_part.ensure( np * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
+    // (the larger of the two layouts: a plain iteration's k_plain_moments leaves plain_moment_blocks partials per moment)
+    if( ( rc = g_ws.mom_part.ensure( np * (size_t)std::max( CB.n_blk * 4, plain_moment_blocks( cx.L.max_tiles ) ) * ICP_NMOM * 8 ) ) ) return rc;
     cx.L.mom_part = g_ws.mom_part.as<double>();
     break;
   }
@@ -1221,7 +1230,7 @@ int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
     if( ( rc = replay_prepare( RB, n, max_n ) ) ) return rc;
     CB.n_seg = chain_segments( max_n ); CB.n_blk = chain_blocks( max_n ); CB.refresh = 0;
     if( ( rc = g_ws.ch_rec.ensure( pts * REC_F4 * 16 ) ) || ( rc = g_ws.ch_done.ensure( np * 8 ) ) ||
-        ( rc = g_ws.mom_part.ensure( np * CB.n_blk * 4 * ICP_NMOM * 8 ) ) ) return rc;
+        ( rc = g_ws.mom_part.ensure( np * (size_t)std::max( CB.n_blk * 4, plain_moment_blocks( cx.L.max_tiles ) ) * ICP_NMOM * 8 ) ) ) return rc;
     if( int rcf = icp_fill( g_ws.ch_done.p, 0, np * 8 ) ) return rcf;
     CB.done = g_ws.ch_done.as<int>();
     cx.L.rec = (float4*)g_ws.ch_rec.p;
@@ -1253,7 +1262,13 @@ int icp_step( IcpCtx& cx, IcpEst& E, int i )
     if( i < E.n_plain )
     {
       IcpLaunch Lp = cx.L; Lp.exact_centroids = 0;
-      launch_icp_plain_from_records( Lp, E.CB, g_stream );
+      if( Lp.rec ) launch_icp_plain_from_records( Lp, E.CB, g_stream );
+      else
+      {
+        // (its search ran without records, icp_align_impl: the moments from the matches, one partial per workgroup)
+        Lp.n_mom_blocks = plain_moment_blocks( Lp.max_tiles );
+        launch_icp_plain_from_matches( Lp, E.CB, g_stream );
+      }
       return RS_HIP_ICP_STEP_PLAIN;
     }
     if( E.est == ICP_EST_RECORDS ) { launch_icp_exact_centroids_from_records( cx.L, E.RB, E.CB, g_stream ); break; }
@@ -1378,6 +1393,9 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
   static const long long coop_all_below = getenv( "RS_HIP_COOP_ALL_BELOW" ) ? atoll( getenv( "RS_HIP_COOP_ALL_BELOW" ) ) : 4096;
   static const int coop_waves_forced = getenv( "RS_HIP_COOP_WAVES" ) ? atoi( getenv( "RS_HIP_COOP_WAVES" ) ) : 0;
   cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
+  // (per ITERATION, not per chunk or call: a traced call runs one iteration per chunk, and the RECORDS estimator's own iterations follow plain ones)
+  float4* const rec_all = cx.L.rec;
+  const bool plain_matches = !g_plain_records.load() && ( E.est == ICP_EST_GRID_CHAINS || E.est == ICP_EST_RECORDS );
   if( ( rc = icp_fills_flush() ) ) return rc;      // everything the call's first kernels expect zeroed, in one launch
   ProfChain prof;
   int kind = RS_HIP_ICP_STEP_NONE;                  // (rs_hip_icp_trace_begin: the estimator of the iteration just enqueued)
@@ -1402,6 +1420,7 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
         cx.L.heavy_in = i == 0 ? nullptr : ( ( i & 1 ) ? g_ws.order_a.as<int>() : g_ws.order_b.as<int>() );
         cx.L.heavy_out = ( i & 1 ) ? g_ws.order_b.as<int>() : g_ws.order_a.as<int>();
       }
+      cx.L.rec = ( plain_matches && i < E.n_plain ) ? nullptr : rec_all;      // a plain iteration's search leaves slot, dist² and dot only
       if( debug ) icp_debug_before( cx, n );
       prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
       if( debug ) icp_debug_after( cx, cx.L.max_n, n, i, max_dist );
@@ -1422,9 +1441,8 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
   bool gave_up = false;
   if( E.est == ICP_EST_GRID_CHAINS )
   {
-    std::vector<int> failed( np );
-    HIP_TRY( hipMemcpy( failed.data(), E.CB.failed, np * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
-    for( int p = 0; p < n; ++p ) gave_up = gave_up || failed[p] != 0;
+    const int* hFailed = (const int*)( hS + np * ICP_ST_FAILED );      // (part of the state block the loop's last look copied)
+    for( int p = 0; p < n; ++p ) gave_up = gave_up || hFailed[p] != 0;
   }
   if( !srcs ) icp_debug_report( E, n, centroid_mode, gave_up );
   if( gave_up ) { g_chains_gave_up.fetch_add( 1 ); return ICP_CHAINS_GAVE_UP; }      // (nothing written to the caller's arrays yet)
@@ -1562,6 +1580,12 @@ int32_t rs_hip_icp_early_plain( int32_t on )
 {
   const int prev = g_early_plain.load();
   if( on >= 0 ) g_early_plain.store( on ? 1 : 0 );
+  return prev;
+}
+int32_t rs_hip_icp_plain_from_records( int32_t on )
+{
+  const int prev = g_plain_records.load();
+  if( on >= 0 ) g_plain_records.store( on ? 1 : 0 );
   return prev;
 }
 float rs_hip_icp_stop_guard( float guard )

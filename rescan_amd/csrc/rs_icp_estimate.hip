@@ -16,6 +16,29 @@ namespace rs {
 //   [34] Σw·e²,  e = (p-q)·n
 // ------------------------------------------------------------------------------------------
 
+// One correspondence's share of the 35 moments above: weight w, source point p in the target's frame, matched target point q4 and normal n4
+// (shared by k_icp_moments and k_plain_moments: the same expressions, so the same addends).
+__device__ __forceinline__ void moments_add( double ( &acc )[ICP_NMOM], float w, float px, float py, float pz, const float4& q4, const float4& n4 )
+{
+  const double W = w, p[3] = { px, py, pz }, q[3] = { q4.x, q4.y, q4.z }, n[3] = { n4.x, n4.y, n4.z };
+  const double a[3] = { p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0] };
+  const double e = ( p[0] - q[0] ) * n[0] + ( p[1] - q[1] ) * n[1] + ( p[2] - q[2] ) * n[2];
+  acc[0] += W;
+  acc[1] += W * p[0]; acc[2] += W * p[1]; acc[3] += W * p[2];
+  acc[4] += W * q[0]; acc[5] += W * q[1]; acc[6] += W * q[2];
+  acc[7]  += W * a[0] * a[0]; acc[8]  += W * a[0] * a[1]; acc[9]  += W * a[0] * a[2];
+  acc[10] += W * a[1] * a[1]; acc[11] += W * a[1] * a[2]; acc[12] += W * a[2] * a[2];
+#pragma unroll
+  for( int r = 0; r < 3; ++r )
+#pragma unroll
+    for( int c = 0; c < 3; ++c ) acc[13 + 3 * r + c] += W * a[r] * n[c];
+  acc[22] += W * n[0] * n[0]; acc[23] += W * n[0] * n[1]; acc[24] += W * n[0] * n[2];
+  acc[25] += W * n[1] * n[1]; acc[26] += W * n[1] * n[2]; acc[27] += W * n[2] * n[2];
+  acc[28] += W * a[0] * e; acc[29] += W * a[1] * e; acc[30] += W * a[2] * e;
+  acc[31] += W * n[0] * e; acc[32] += W * n[1] * e; acc[33] += W * n[2] * e;
+  acc[34] += W * e * e;
+}
+
 __global__ __launch_bounds__( BLOCK ) void k_icp_moments( IcpLaunch L )
 {
   __shared__ double red[WAVES_PER_BLOCK][ICP_NMOM];
@@ -75,23 +98,7 @@ __global__ __launch_bounds__( BLOCK ) void k_icp_moments( IcpLaunch L )
     xform3( T1, p4.x, p4.y, p4.z, 1.0f, tx, ty, tz );
     xform3( L.T2i, tx, ty, tz, 1.0f, px, py, pz );
     const float4 q4 = L.tgt.pos[slot], n4 = L.tgt.nor[slot];
-    const double W = w, p[3] = { px, py, pz }, q[3] = { q4.x, q4.y, q4.z }, n[3] = { n4.x, n4.y, n4.z };
-    const double a[3] = { p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0] };
-    const double e = ( p[0] - q[0] ) * n[0] + ( p[1] - q[1] ) * n[1] + ( p[2] - q[2] ) * n[2];
-    acc[0] += W;
-    acc[1] += W * p[0]; acc[2] += W * p[1]; acc[3] += W * p[2];
-    acc[4] += W * q[0]; acc[5] += W * q[1]; acc[6] += W * q[2];
-    acc[7]  += W * a[0] * a[0]; acc[8]  += W * a[0] * a[1]; acc[9]  += W * a[0] * a[2];
-    acc[10] += W * a[1] * a[1]; acc[11] += W * a[1] * a[2]; acc[12] += W * a[2] * a[2];
-#pragma unroll
-    for( int r = 0; r < 3; ++r )
-#pragma unroll
-      for( int c = 0; c < 3; ++c ) acc[13 + 3 * r + c] += W * a[r] * n[c];
-    acc[22] += W * n[0] * n[0]; acc[23] += W * n[0] * n[1]; acc[24] += W * n[0] * n[2];
-    acc[25] += W * n[1] * n[1]; acc[26] += W * n[1] * n[2]; acc[27] += W * n[2] * n[2];
-    acc[28] += W * a[0] * e; acc[29] += W * a[1] * e; acc[30] += W * a[2] * e;
-    acc[31] += W * n[0] * e; acc[32] += W * n[1] * e; acc[33] += W * n[2] * e;
-    acc[34] += W * e * e;
+    moments_add( acc, w, px, py, pz, q4, n4 );
   }
   const int lane = threadIdx.x & ( WAVE - 1 ), wib = threadIdx.x / WAVE;
 #pragma unroll
@@ -1323,6 +1330,101 @@ __global__ __launch_bounds__( BLOCK ) void k_chain_moments( IcpLaunch L, ChainBu
   chain_moments_block( L, B, prob, blockIdx.x, S, L.rec + (size_t)prob * L.src.n * REC_F4 );
 }
 
+// The plain step's moments WITHOUT records (round 10): what a plain iteration needs of a correspondence is its weight and the 35 addends,
+// in no particular order — so its search writes no 48-byte record (L.rec == null: slot, dist² and dot only, 12 B per point, coalesced by
+// query slot) and this kernel forms the addends from what the search leaves for everyone else: one wave per source tile, the source point
+// under the current pose by icp_query's float operations, the match's position and normal gathered from the target.  The weight is
+// chain_addends', the addends are moments_add's: every addend has the bits k_chain_moments gives it, only the order of the fp64
+// additions differs — and that order is a function of the launch's shape alone (wave w of workgroup b takes the tiles
+// plain_first + k * plain_stride of its range, lanes are added by wave_sums, the four waves in turn, the workgroups' partials by
+// k_icp_update_wide): two runs give the same bits.
+// The tiles are walked as the search walks them (k_icp_corr: natural_tile): workgroups are dealt round-robin over the 8 XCDs, and
+// XCD class c = b mod 8 takes the c-th eighth of the source's (Hilbert) tile order, so the target lines an XCD gathers are the ones its
+// L2 holds from the search.  RS_PLAIN_XCD=0: plain striding (measurements).
+#ifndef RS_PLAIN_XCD
+#define RS_PLAIN_XCD 1
+#endif
+#ifndef RS_PLAIN_MAX_BLOCKS
+#define RS_PLAIN_MAX_BLOCKS 512
+#endif
+constexpr int PLAIN_MAX_BLOCKS = RS_PLAIN_MAX_BLOCKS;     // workgroups per problem at most: four per CU, 35 x 1 024 partials for k_icp_update_wide instead of 35 x n / 1 024
+constexpr int PLAIN_TILES_PER_WAVE = 4;    // ... and no fewer tiles per wave than this while the grid is below that
+int plain_moment_blocks( int n_tiles )
+{
+  const int b = ( std::max( n_tiles, 1 ) + WAVES_PER_BLOCK * PLAIN_TILES_PER_WAVE - 1 ) / ( WAVES_PER_BLOCK * PLAIN_TILES_PER_WAVE );
+  return std::min( PLAIN_MAX_BLOCKS, ( b + 7 ) & ~7 );        // (a multiple of 8: every XCD class gets the same number of workgroups)
+}
+__global__ __launch_bounds__( BLOCK ) void k_plain_moments( IcpLaunch L )
+{
+  RS_CHAIN_SETPRIO();
+  __shared__ double red[WAVES_PER_BLOCK][ICP_NMOM];
+  __shared__ unsigned long long s_stat[WAVES_PER_BLOCK][3];
+  const int prob = blockIdx.y;
+  if( L.active[prob] == 0 ) return;
+  icp_bind( L, prob );
+  // (block 0 leaves n, mean, stddev and the queue's length in L.res for icp_update_tail, as chain_moments_block does)
+  const float sd = chain_stats( L, prob, s_stat, ( blockIdx.x == 0 && threadIdx.x == 0 ) ? L.res + (size_t)prob * ICP_NRES + ICP_NMOM : nullptr );
+  const bool use_sd = sd > 0.000001;
+  const float cut = 2.5f * sd;
+  Xform T1;
+#pragma unroll
+  for( int k = 0; k < 16; ++k ) T1.m[k] = L.T1[prob * 16 + k];
+  const int lane = threadIdx.x & ( WAVE - 1 ), wib = uni( (int)threadIdx.x / WAVE );
+  const int n_tiles = L.src.n_tiles;
+#if RS_PLAIN_XCD
+  const int per = ( n_tiles + 7 ) / 8, cls = (int)blockIdx.x & 7;
+  const int t_end = min( n_tiles, ( cls + 1 ) * per ), stride = ( (int)gridDim.x >> 3 ) * WAVES_PER_BLOCK;
+  int t = cls * per + ( (int)blockIdx.x >> 3 ) * WAVES_PER_BLOCK + wib;
+#else
+  const int t_end = n_tiles, stride = (int)gridDim.x * WAVES_PER_BLOCK;
+  int t = (int)blockIdx.x * WAVES_PER_BLOCK + wib;
+#endif
+
+  double acc[ICP_NMOM];
+#pragma unroll
+  for( int k = 0; k < ICP_NMOM; ++k ) acc[k] = 0.0;
+  // what a lane reads of its point by query slot (coalesced); the next tile's are on their way while this tile's gathers are
+  struct Pt { int slot; float d2, dot; float4 p; };
+  auto fetch = [&]( int tt ) -> Pt
+  {
+    Pt r; r.slot = -1; r.d2 = 0.0f; r.dot = 0.0f; r.p = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
+    if( tt < t_end )
+    {
+      const int i = (int)L.src.tiles[tt] + lane;
+      if( i < (int)L.src.tiles[tt + 1] )
+      {
+        const size_t o = (size_t)L.pt_off + i;
+        r.slot = L.m_slot[o]; r.d2 = L.m_d2[o]; r.dot = L.m_dot[o]; r.p = L.src.pos[i];
+      }
+    }
+    return r;
+  };
+  Pt cur = fetch( t );
+  for( ; t < t_end; t += stride )
+  {
+    const Pt nxt = fetch( t + stride );
+    if( cur.slot >= 0 )
+    {
+      const float4 q4 = L.tgt.pos[cur.slot], n4 = L.tgt.nor[cur.slot];
+      float w = ( 1.0f - __fdiv_rn( cur.d2, L.radius ) ) * cur.dot;         // chain_addends' weight (icp.h:387,396-401)
+      if( use_sd && cur.d2 > cut ) w = 0.0f;
+      float tx, ty, tz, px, py, pz;
+      xform3( T1, cur.p.x, cur.p.y, cur.p.z, 1.0f, tx, ty, tz );           // icp_query's float operations
+      xform3( L.T2i, tx, ty, tz, 1.0f, px, py, pz );
+      moments_add( acc, w, px, py, pz, q4, n4 );
+    }
+    cur = nxt;
+  }
+  { const double v = wave_sums( acc, lane ); if( lane < ICP_NMOM ) red[wib][lane] = v; }
+  __syncthreads();
+  if( threadIdx.x < ICP_NMOM )
+  {
+    double v = 0.0;
+    for( int w = 0; w < WAVES_PER_BLOCK; ++w ) v += red[w][threadIdx.x];
+    L.mom_part[( (size_t)prob * ICP_NMOM + threadIdx.x ) * L.n_mom_blocks + blockIdx.x] = v;      // (moment-major, as k_chain_moments: L.n_mom_blocks == gridDim.x)
+  }
+}
+
 #define CH_M_LO ( 1 << 23 )
 #define CH_M_HI ( ( 1 << 24 ) - 1 )
 // A record's function for one exponent is  M -> M + D, valid for lo <= M <= hi  (lo > hi: never).  A run of records f_0 .. f_l
@@ -2492,6 +2594,14 @@ void launch_icp_plain_from_records( const IcpLaunch& L, const ChainBufs& B, hipS
 {
   ChainBufs Bq = B; Bq.refresh = 0;
   hipLaunchKernelGGL( k_chain_moments, dim3( B.n_blk * CH_QUARTERS, L.n_prob ), dim3( BLOCK ), 0, st, L, Bq );
+  hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, B.done );
+}
+
+// The same step from the searches' matches (L.rec == null in its search: no records written): k_plain_moments' partials, one per
+// workgroup — L.n_mom_blocks must be plain_moment_blocks( L.max_tiles ).
+void launch_icp_plain_from_matches( const IcpLaunch& L, const ChainBufs& B, hipStream_t st )
+{
+  hipLaunchKernelGGL( k_plain_moments, dim3( L.n_mom_blocks, L.n_prob ), dim3( BLOCK ), 0, st, L );
   hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, B.done );
 }
 

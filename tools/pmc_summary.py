@@ -45,7 +45,7 @@ def per_domain(path, counters=None):
             dom = "nn_icp"
             if "coop" not in n:
                 out[dom]["units"] += 1
-        elif any(x in n for x in ("k_icp_moments", "k_icp_update", "k_chain_", "k_replay_", "k_icp_faith", "k_lane_")):
+        elif any(x in n for x in ("k_icp_moments", "k_plain_moments", "k_icp_update", "k_chain_", "k_replay_", "k_icp_faith", "k_lane_")):
             dom = "icp_moments"
             if "k_icp_update" in n or "k_icp_faithful" in n or "k_replay_finish" in n or "k_lane_walk_and_update" in n:
                 out[dom]["units"] += 1
@@ -117,7 +117,7 @@ if __name__ == "__main__":
         def total(names):
             return sum((2 * F[k][0] + W.get(k, (0, 0))[0]) * F[k][1] for k in F if any(n in k for n in names)) * 1024
         # domain -> (kernels that belong to it, kernels whose launches count as ONE unit of it)
-        doms = {"nn_icp": (["k_icp_corr"], ["k_icp_corr<"]), "icp_moments": (["k_icp_moments", "k_icp_update", "k_chain_", "k_lane_"], ["k_icp_update", "k_lane_walk_and_update"]),       # the estimator: one k_icp_update per iteration (round 3: + the centroid chains' kernels)
+        doms = {"nn_icp": (["k_icp_corr"], ["k_icp_corr<"]), "icp_moments": (["k_icp_moments", "k_plain_moments", "k_icp_update", "k_chain_", "k_lane_"], ["k_icp_update", "k_lane_walk_and_update"]),       # the estimator: one k_icp_update per iteration (round 3: + the centroid chains' kernels)
                 "nn_score": (["k_score"], ["rs::k_score<"]), "nn_label": (["k_label"], ["rs::k_label("])}
         out = {"_note": "HBM-side bytes per launch from rocprofv3 PMC (separate FETCH_SIZE and WRITE_SIZE passes of `bench.py --steps 2 "
                         "--warmup 1 --serial`, tools/profile.sh traffic, folded by tools/pmc_summary.py --fold), FETCH_SIZE doubled as "
