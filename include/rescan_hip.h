@@ -217,6 +217,14 @@ int32_t rs_hip_icp_early_plain( int32_t on );
  * additions differs).  on = 1 (environment RS_HIP_PLAIN_RECORDS=1) brings the plain step from records back: for A/B runs and tests.
  * on < 0 only reads; returns the previous setting.  The trace kind of both is RS_HIP_ICP_STEP_PLAIN. */
 int32_t rs_hip_icp_plain_from_records( int32_t on );
+/* The launch that ends an iteration of a scan-sized source (35 workgroups sum the moments' partials, the last one to finish solves)
+ * hands its 35 sums over by agent-scope atomic stores, a relaxed ticket and atomic loads.  on = 1 (environment RS_HIP_UPDATE_FENCED=1)
+ * brings back the hand-over by two full memory fences: the same bits, for A/B runs and tests.  on < 0 only reads; returns the previous
+ * setting. */
+int32_t rs_hip_icp_update_fenced( int32_t on );
+/* (tests) The loop state an ICP call keeps on the device: 4-byte words per problem, and the largest state block, in words, that is written by
+ * the call's fill launch from its argument block (larger batches: a host-to-device copy).  The results do not depend on which. */
+void    rs_hip_icp_state_layout( int32_t* words_per_problem, int32_t* launch_max_words );
 float   rs_hip_icp_stop_guard( float guard );      /* sets the guard's width (0: off); < 0 only reads; returns the previous width */
 /* The sequential estimator (sources up to rs_hip_icp_reference_order_below) runs the reference's dist² statistics and its weighted
  * centroids in ONE pass, the 2.5 sigma cut of the weights (lib/rs/icp.h:396-401) taken at a guess of sigma; the pass stands when no

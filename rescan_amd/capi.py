@@ -57,6 +57,8 @@ SIGNATURES = {
     "rs_hip_icp_stop_guard": (C.c_float, [C.c_float]),
     "rs_hip_icp_early_plain": (C.c_int32, [C.c_int32]),
     "rs_hip_icp_plain_from_records": (C.c_int32, [C.c_int32]),
+    "rs_hip_icp_update_fenced": (C.c_int32, [C.c_int32]),
+    "rs_hip_icp_state_layout": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rs_hip_icp_replay_redone": (C.c_int32, []),
     "rs_hip_icp_faith_redone": (C.c_int32, []),
     "rs_hip_icp_faith_guess": (C.c_int32, [C.c_int32]),
@@ -634,6 +636,19 @@ def icp_plain_from_records(on=-1):
     """1: plain iterations read the searches' 48-byte records again (default 0: moments from the matches, no records written); -1 only reads.
     Returns the previous setting."""
     return int(load().rs_hip_icp_plain_from_records(int(on)))
+
+
+def icp_update_fenced(on=-1):
+    """1: the launch that ends an iteration hands its sums over by two full fences again (default 0: agent-scope atomics; the same bits);
+    -1 only reads.  Returns the previous setting."""
+    return int(load().rs_hip_icp_update_fenced(int(on)))
+
+
+def icp_state_layout():
+    """(words of loop state per problem, largest state block in words that rides in the fill launch's argument block)."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    load().rs_hip_icp_state_layout(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
 
 
 def icp_stop_guard(guard=-1.0):

@@ -748,24 +748,32 @@ static rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, in
 // launch.  Each was a hipMemsetAsync — a kernel of the runtime's, 7-9 us apart on the stream: ten of them put 84 us in front of the first
 // search of every call (profiles/r06/trace_one_serial_step.txt before this), 3 % of the headline's step.
 namespace rs {
-struct FillRanges { static constexpr int MAX = 16; uint32_t* p[MAX]; unsigned long long words[MAX]; uint32_t value[MAX]; int n; };
+// ... and the call's initial loop state (round 11): a state block of up to STATE_MAX words — six problems — rides in the launch's argument
+// block and is written from there, instead of a host-to-device copy packet of its own in front of the launch (icp_upload_state).
+struct FillRanges
+{
+  static constexpr int MAX = 16, STATE_MAX = 256;
+  uint32_t* p[MAX]; unsigned long long words[MAX]; uint32_t value[MAX]; int n;
+  uint32_t* state_dst; int state_words; uint32_t state[STATE_MAX];
+};
 __global__ __launch_bounds__( 256 ) void k_fill_ranges( FillRanges R )
 {
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x, step = (size_t)gridDim.x * 256;
   for( int r = 0; r < R.n; ++r )
     for( size_t i = t; i < R.words[r]; i += step ) R.p[r][i] = R.value[r];
+  if( blockIdx.x == 0 && (int)threadIdx.x < R.state_words ) R.state_dst[threadIdx.x] = R.state[threadIdx.x];
 }
 }
 namespace {
 thread_local rs::FillRanges g_fills{};
 int icp_fills_flush()
 {
-  if( g_fills.n == 0 ) return RS_HIP_OK;
+  if( g_fills.n == 0 && g_fills.state_words == 0 ) return RS_HIP_OK;
   unsigned long long most = 0;
   for( int r = 0; r < g_fills.n; ++r ) most = std::max( most, g_fills.words[r] );
   const int blocks = (int)std::min<unsigned long long>( 1024ull, std::max<unsigned long long>( 1ull, ( most + 1023 ) / 1024 ) );
   hipLaunchKernelGGL( rs::k_fill_ranges, dim3( blocks ), dim3( 256 ), 0, g_stream, g_fills );
-  g_fills.n = 0;
+  g_fills.n = 0; g_fills.state_words = 0;
   return RS_HIP_OK;      // (a failed launch surfaces at the call's synchronisation, like every other kernel's)
 }
 // hipMemsetAsync( p, byte, bytes, g_stream ), deferred to the call's one fill launch (icp_fills_flush: before the first kernel that reads p)
@@ -909,7 +917,7 @@ int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tg
     cx.heavy_words = np * heavy_stride( src->qview.n_tiles );
   }
   cx.n_waves = L.max_tiles;
-  L.n_mom_blocks = std::max( 1, std::min( 512, ( L.max_n + 255 ) / 256 ) );    // 512: gathers want more waves in flight than 256 give, the final tree fewer partials than 1024
+  L.n_mom_blocks = std::max( 1, std::min( 512, ( L.max_n + 255 ) / 256 ) );    // (the fp64 moments' own grid; a plain iteration's is plain_moment_blocks: at most 512 workgroups too)
   if( ( rc = g_ws.state.ensure( np * ICP_STATE_WORDS * 4 ) ) ||
       ( rc = g_ws.slot.ensure( cx.total_pts * 4 ) ) || ( rc = g_ws.d2.ensure( cx.total_pts * 4 ) ) || ( rc = g_ws.dot.ensure( cx.total_pts * 4 ) ) ||
       ( rc = g_ws.stat_acc.ensure( np * STAT_SHARDS * 4 * 8 ) ) ||
@@ -949,7 +957,7 @@ int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tg
   }
   L.faith_redone = g_faith_redone.as<int>();
   L.faith_guess_scale = (float)g_faith_guess_permille.load() / 1000.0f;
-  g_fills.n = 0;      // (fills an earlier call queued and never launched — it failed before its first kernel — are not this call's)
+  g_fills.n = 0; g_fills.state_words = 0;      // (fills an earlier call queued and never launched — it failed before its first kernel — are not this call's)
   if( int rcf = icp_fill( g_ws.queue_count.p, 0, np * 4 ) ) return rcf;
   return RS_HIP_OK;
 }
@@ -981,10 +989,12 @@ int replay_prepare( ReplayBufs& B, int n_prob, int n_source )
   return RS_HIP_OK;
 }
 
-// initial loop state (icp.h:441-442: errors start at 1e6)
+// initial loop state (icp.h:441-442: errors start at 1e6): with the call's fill launch when it fits in its argument block (the launch
+// is enqueued by icp_fills_flush, before the first kernel of the call), else by a copy from the pinned block
 int icp_upload_state( IcpCtx& cx, const float* T1s, size_t np )
 {
-  float* h = g_ws.h_b.as<float>();
+  const bool by_launch = np * ICP_STATE_WORDS <= (size_t)rs::FillRanges::STATE_MAX;
+  float* h = by_launch ? reinterpret_cast<float*>( g_fills.state ) : g_ws.h_b.as<float>();
   std::memset( h, 0, np * ICP_STATE_WORDS * 4 );
   int* hi = (int*)h;
   for( size_t p = 0; p < np; ++p )
@@ -992,6 +1002,12 @@ int icp_upload_state( IcpCtx& cx, const float* T1s, size_t np )
     std::memcpy( h + np * ICP_ST_T1 + 16 * p, T1s + 16 * p, 64 ); hi[np * ICP_ST_ACTIVE + p] = 1;
     std::memcpy( h + np * ICP_ST_T1_PREV + 16 * p, T1s + 16 * p, 64 );
     h[np * ICP_ST_ERR + p] = 1e6f; h[np * ICP_ST_PREV_ERR + p] = 1e6f;
+  }
+  if( by_launch )
+  {
+    // (the pinned block too: a call that enqueues no iteration — max_iter <= 0 — reads its results from there without a copy back)
+    std::memcpy( g_ws.h_b.as<float>(), h, np * ICP_STATE_WORDS * 4 );
+    g_fills.state_dst = g_ws.state.as<uint32_t>(); g_fills.state_words = (int)( np * ICP_STATE_WORDS ); return RS_HIP_OK;
   }
   HIP_TRY( hipMemcpyAsync( g_ws.state.p, h, np * ICP_STATE_WORDS * 4, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
   return RS_HIP_OK;
@@ -1588,6 +1604,12 @@ int32_t rs_hip_icp_plain_from_records( int32_t on )
   if( on >= 0 ) g_plain_records.store( on ? 1 : 0 );
   return prev;
 }
+int32_t rs_hip_icp_update_fenced( int32_t on ) { return icp_update_fenced( on ); }
+void rs_hip_icp_state_layout( int32_t* words_per_problem, int32_t* launch_max_words )
+{
+  if( words_per_problem ) *words_per_problem = ICP_STATE_WORDS;
+  if( launch_max_words ) *launch_max_words = rs::FillRanges::STATE_MAX;
+}
 float rs_hip_icp_stop_guard( float guard )
 {
   const float prev = g_stop_guard.load();
@@ -1763,7 +1785,7 @@ int rs_hip_icp_estimate_pt2pl( const float* pts1, const float* pts2, const float
 {
   int rc = ensure_ready(); if( rc ) return rc;
   if( !pts1 || !pts2 || !nor2 || !weights || !T1 || n <= 0 ) { set_err( "icp_estimate: bad arguments" ); return RS_HIP_E_ARG; }
-  g_fills.n = 0;      // (see icp_prepare)
+  g_fills.n = 0; g_fills.state_words = 0;      // (see icp_prepare)
   // Present the correspondences to k_icp_moments as "query i matched slot i" with explicit weights.
   const size_t nn = (size_t)n;
   if( ( rc = g_ws.tmp_pos.ensure( nn * 16 ) ) || ( rc = g_ws.tmp_pos2.ensure( nn * 16 ) ) || ( rc = g_ws.tmp_nor2.ensure( nn * 16 ) ) ||

@@ -1,6 +1,9 @@
 // librescan_hip device code (gfx950, wave64) — the ICP estimators: fp64 moments, reference-order chains, replay, grid chains (lib/rs/icp.h:136-148,210-298)
 #include "rs_search.h"
 #include "rs_icp.h"
+#include "rs_tail_dbg.h"      // TD_STAMP: phase stamps of the kernels that end an iteration (diagnostic builds; nothing otherwise)
+#include <atomic>
+#include <cstdlib>
 
 namespace rs {
 
@@ -113,38 +116,63 @@ __global__ __launch_bounds__( BLOCK ) void k_icp_moments( IcpLaunch L )
 
 }
 
-// The rest of an iteration once the moments are summed in L.res (the whole workgroup comes in; thread 0 solves).
-__device__ __forceinline__ void icp_update_tail( const IcpLaunch& L, int prob )
+// The rest of an iteration once the moments are summed (icp.h:455-493), in two halves: what it reads that the launch which ends the
+// iteration does not itself write — the state words, n_corr, the chains' totals: all left by earlier launches, or by the workgroup's
+// own waves before its barrier — and the solve with everything it writes.  k_icp_update_wide loads the first half before it knows
+// that it is the workgroup which goes on.
+struct IcpTailIn { float T1[16]; float err; int iters; double n_corr; double cen[7]; };
+__device__ __forceinline__ IcpTailIn icp_tail_inputs( const IcpLaunch& L, int prob )
 {
-  double* res = L.res + (size_t)prob * ICP_NRES;
-  if( !L.solve ) return;
-  icp_iteration_reset( L, prob );
-  if( threadIdx.x != 0 ) return;
+  IcpTailIn in;
+#pragma unroll
+  for( int k = 0; k < 16; ++k ) in.T1[k] = L.T1[prob * 16 + k];
+  in.err = L.err[prob]; in.iters = L.iters[prob];
+  in.n_corr = L.res[(size_t)prob * ICP_NRES + ICP_NMOM];
+  const double* t2 = L.centroid_totals + ( (size_t)prob * 3 + 1 ) * ICP_NMOM;
+#pragma unroll
+  for( int a = 0; a < 7; ++a ) in.cen[a] = L.exact_centroids ? t2[a] : 0.0;
+  return in;
+}
+// (thread 0 of the workgroup that ends the iteration; res: the 35 summed moments; dbg: diagnostic builds' stamps, else null)
+__device__ __forceinline__ void icp_tail_finish( const IcpLaunch& L, int prob, const IcpTailIn& in, const double* res, unsigned long long* dbg = nullptr )
+{
   // ---- icp.h:455-493 for this problem ----
-  L.prev_err[prob] = L.err[prob];
-  L.iters[prob] += 1;
-  if( res[ICP_NMOM] == 0.0 ) { L.active[prob] = 0; return; }            // icp.h:455-459: no correspondences
+  L.prev_err[prob] = in.err;
+  L.iters[prob] = in.iters + 1;
+  if( in.n_corr == 0.0 ) { L.active[prob] = 0; return; }              // icp.h:455-459: no correspondences
   Mat4 T;
-  for( int k = 0; k < 16; ++k ) { T.m[k] = L.T1[prob * 16 + k]; L.T1_prev[prob * 16 + k] = T.m[k]; }
+  for( int k = 0; k < 16; ++k ) { T.m[k] = in.T1[k]; L.T1_prev[prob * 16 + k] = T.m[k]; }
   float e;
   float cen[6];
   if( L.exact_centroids )
   {
     // the reference's own centroids: c = Σw·p * ( 1.0f / Σw ), every sum its sequential fp32 chain (icp.h:136-148)
-    const double* t2 = L.centroid_totals + ( (size_t)prob * 3 + 1 ) * ICP_NMOM;
-    const float total = (float)t2[0];
+    const float total = (float)in.cen[0];
     if( total <= 1e-7 ) { L.active[prob] = 0; return; }                 // icp.h:466-470
     const float inv = __fdiv_rn( 1.0f, total );
-    for( int a = 0; a < 6; ++a ) cen[a] = (float)t2[1 + a] * inv;
+    for( int a = 0; a < 6; ++a ) cen[a] = (float)in.cen[1 + a] * inv;
   }
-  if( !icp_solve( res, T, e, L.exact_centroids ? cen : nullptr ) ) { L.active[prob] = 0; return; }         // icp.h:466-470: weights vanished
+  const bool solved = icp_solve( res, T, e, L.exact_centroids ? cen : nullptr );
+  TD_STAMP( dbg, 6 );
+  if( !solved ) { L.active[prob] = 0; return; }                         // icp.h:466-470: weights vanished
   for( int k = 0; k < 16; ++k ) L.T1[prob * 16 + k] = T.m[k];           // icp.h:295
   L.err[prob] = e;
-  const float delta = fabsf( L.prev_err[prob] - e );
+  const float delta = fabsf( in.err - e );
   // (an estimator that is not the reference's own order follows the reference's errors to ~1e-7; a stop test decided by less than
   //  that margin may fall the other way — one iteration more or less, 1e-4 in the pose.  Such a problem is flagged: rs_api.hip)
   if( !L.fixed_iters && L.iter_index > 5 && L.stop_guard > 0.0f && fabsf( delta - 1e-5f ) < L.stop_guard ) L.ticket[prob] = 1;
   if( !L.fixed_iters && L.iter_index > 5 && delta < 1e-5 ) L.active[prob] = 0;   // icp.h:489
+}
+
+// ... for a workgroup whose own barrier stands between the sums in L.res and this call (the whole workgroup comes in; thread 0 solves).
+__device__ __forceinline__ void icp_update_tail( const IcpLaunch& L, int prob, unsigned long long* dbg = nullptr )
+{
+  if( !L.solve ) return;
+  icp_iteration_reset( L, prob );
+  if( threadIdx.x != 0 ) return;
+  const IcpTailIn in = icp_tail_inputs( L, prob );
+  TD_STAMP_LOADED( dbg, 5 );
+  icp_tail_finish( L, prob, in, L.res + (size_t)prob * ICP_NRES, dbg );
 }
 
 // One workgroup per problem: fixed-order sum of the per-workgroup partials (moment k by wave k mod 16;
@@ -187,6 +215,20 @@ __global__ __launch_bounds__( UPDATE_WAVES * WAVE ) void k_icp_update( IcpLaunch
 // workgroup per MOMENT sums its row (a single workgroup took 14 us over the 400 KB of a 1 M-point scan), the last one to finish
 // does the rest of the iteration.  Fixed order throughout: thread t adds partials t, t + 256, ..., then the wave tree, then the
 // four waves in turn.
+// The hand-over inside the launch is ONE double per workgroup.  Each publishes its sum with an agent-scope atomic (write-through) store,
+// waits for it, and draws a relaxed agent-scope ticket; the workgroup whose ticket is the last reads the 35 sums with agent-scope
+// atomic loads, which no CU's L1 serves.  (Until round 11: a plain store and __threadfence() — an L2 write-back and invalidate — before
+// every ticket, and a second one in the last workgroup: FENCED, kept for A/B runs and tests behind rs_hip_icp_update_fenced( 1 ) /
+// RS_HIP_UPDATE_FENCED=1.)  Later launches read L.res and the state as before: the kernel boundary publishes them.
+// What the solve reads besides the sums (icp_tail_inputs) was written by earlier launches: thread 0 of EVERY workgroup asks for it before
+// its partials, so the loads are long back when the last ticket is drawn; and what has to be reset between two searches
+// (icp_iteration_reset) touches nothing the solve reads, so workgroup 0 does it beside the others instead of the last one in front of its solve.
+// Measured (profiles/r11/iteration_tail_breakdown.txt, the last workgroup's path of 9 us): one lane's fence over 8 fresh bytes is cheap —
+// the two together 1.1-1.3 us, the new hand-over 0.7; the load chain that stood behind the second fence 1.0-1.2 -> 0.5-0.8 (the sums alone);
+// the rest of the launch's 13 -> 8.6 us is the reset out of the last workgroup's way and 34 workgroups that no longer fence before they
+// leave.  icp_solve on one lane is 4 of the 8.6.
+#define RS_WAIT_VMCNT0 0x0F70      // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt and lgkmcnt at their maxima)
+template <bool FENCED>
 __global__ __launch_bounds__( BLOCK ) void k_icp_update_wide( IcpLaunch L, int* done )
 {
   RS_CHAIN_SETPRIO();
@@ -195,10 +237,20 @@ __global__ __launch_bounds__( BLOCK ) void k_icp_update_wide( IcpLaunch L, int* 
   const int prob = blockIdx.y, k = blockIdx.x;
   if( L.active[prob] == 0 ) return;
   icp_bind( L, prob );
+#if RS_TAIL_DBG
+  unsigned long long* const dbg = ( prob == 0 && threadIdx.x == 0 ) ? d_upd_dbg[L.iter_index & ( TD_ITERS - 1 )][k] : nullptr;
+  if( dbg ) { dbg[4] = 0ull; dbg[5] = 0ull; dbg[6] = 0ull; }
+#else
+  unsigned long long* const dbg = nullptr;
+#endif
+  TD_STAMP( dbg, 0 );
+  IcpTailIn in{};
+  if( !FENCED && L.solve && threadIdx.x == 0 ) in = icp_tail_inputs( L, prob );
   const int lane = threadIdx.x & ( WAVE - 1 ), wib = threadIdx.x / WAVE;
-  const double* in = L.mom_part + ( (size_t)prob * ICP_NMOM + k ) * L.n_mom_blocks;
+  const double* in_part = L.mom_part + ( (size_t)prob * ICP_NMOM + k ) * L.n_mom_blocks;
+  double* const res = L.res + (size_t)prob * ICP_NRES;
   double v = 0.0;
-  for( int b = threadIdx.x; b < L.n_mom_blocks; b += BLOCK ) v += in[b];
+  for( int b = threadIdx.x; b < L.n_mom_blocks; b += BLOCK ) v += in_part[b];
   v = wave_sum( v );
   if( lane == 0 ) s_part[wib] = v;
   __syncthreads();
@@ -206,15 +258,60 @@ __global__ __launch_bounds__( BLOCK ) void k_icp_update_wide( IcpLaunch L, int* 
   {
     double t = 0.0;
     for( int w = 0; w < WAVES_PER_BLOCK; ++w ) t += s_part[w];
-    L.res[(size_t)prob * ICP_NRES + k] = t;
-    __threadfence();
-    s_last = atomicAdd( done + prob, 1 ) == ICP_NMOM - 1 ? 1 : 0;
+    TD_STAMP( dbg, 1 );
+    if( FENCED )
+    {
+      res[k] = t;
+      __threadfence();
+      TD_STAMP( dbg, 2 );
+      s_last = atomicAdd( done + prob, 1 ) == ICP_NMOM - 1 ? 1 : 0;
+    }
+    else
+    {
+      __hip_atomic_store( res + k, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+      // (the ticket must not pass the sum: the store has left the CU before the add is issued; the signal fences keep the compiler from
+      //  moving either across the wait)
+      __atomic_signal_fence( __ATOMIC_SEQ_CST );
+      __builtin_amdgcn_s_waitcnt( RS_WAIT_VMCNT0 );
+      __atomic_signal_fence( __ATOMIC_SEQ_CST );
+      TD_STAMP( dbg, 2 );
+      s_last = __hip_atomic_fetch_add( done + prob, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) == ICP_NMOM - 1 ? 1 : 0;
+    }
+    TD_STAMP( dbg, 3 );
   }
   __syncthreads();
-  if( !s_last ) return;
-  __threadfence();                                       // (the other workgroups' sums)
-  if( threadIdx.x == 0 ) done[prob] = 0;
-  icp_update_tail( L, prob );
+  if( FENCED )
+  {
+    if( !s_last ) return;
+    __threadfence();                                       // (the other workgroups' sums)
+    TD_STAMP( dbg, 4 );
+    if( threadIdx.x == 0 ) done[prob] = 0;
+    icp_update_tail( L, prob, dbg );
+    return;
+  }
+  if( k == 0 && L.solve ) icp_iteration_reset( L, prob );
+  if( !s_last || threadIdx.x != 0 ) return;
+  __hip_atomic_store( done + prob, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );      // (zero between launches; a call's first fill zeroes it too)
+  if( !L.solve ) return;
+  double m[ICP_NMOM];
+#pragma unroll
+  for( int j = 0; j < ICP_NMOM; ++j ) m[j] = __hip_atomic_load( res + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT );
+  TD_STAMP_LOADED( dbg, 5 );
+  icp_tail_finish( L, prob, in, m, dbg );
+}
+namespace {
+std::atomic<int> g_update_fenced{ getenv( "RS_HIP_UPDATE_FENCED" ) ? atoi( getenv( "RS_HIP_UPDATE_FENCED" ) ) : 0 };
+void launch_icp_update_wide( const IcpLaunch& L, int* done, hipStream_t st )
+{
+  if( g_update_fenced.load() ) hipLaunchKernelGGL( k_icp_update_wide<true>, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, done );
+  else hipLaunchKernelGGL( k_icp_update_wide<false>, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, done );
+}
+}
+int icp_update_fenced( int on )
+{
+  const int prev = g_update_fenced.load();
+  if( on >= 0 ) g_update_fenced.store( on ? 1 : 0 );
+  return prev;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1347,7 +1444,10 @@ __global__ __launch_bounds__( BLOCK ) void k_chain_moments( IcpLaunch L, ChainBu
 #ifndef RS_PLAIN_MAX_BLOCKS
 #define RS_PLAIN_MAX_BLOCKS 512
 #endif
-constexpr int PLAIN_MAX_BLOCKS = RS_PLAIN_MAX_BLOCKS;     // workgroups per problem at most: four per CU, 35 x 1 024 partials for k_icp_update_wide instead of 35 x n / 1 024
+constexpr int PLAIN_MAX_BLOCKS = RS_PLAIN_MAX_BLOCKS;     // workgroups per problem at most: two per CU (two waves per SIMD), 35 x 512 partials for k_icp_update_wide instead of 35 x n / 1 024.
+// (With two waves on a SIMD the kernel is bound by its fp64 instructions — ~280 per tile and wave, 4 cycles each: while one wave waits for
+//  its gathers the other adds.  Round 11 tried the loads as a pipeline ahead of the arithmetic — gathers one tile ahead, point words two,
+//  counted waits — and 1 024 workgroups again: 14.5 against 14.8 us alone on the chip, nothing in the bench; 1 024: slower.  DESIGN §3.)
 constexpr int PLAIN_TILES_PER_WAVE = 4;    // ... and no fewer tiles per wave than this while the grid is below that
 int plain_moment_blocks( int n_tiles )
 {
@@ -1399,7 +1499,14 @@ __global__ __launch_bounds__( BLOCK ) void k_plain_moments( IcpLaunch L )
     }
     return r;
   };
+#if RS_TAIL_DBG
+  const int td_wave = (int)blockIdx.x * WAVES_PER_BLOCK + wib;
+  unsigned long long* const dbg = ( prob == 0 && lane == 0 && td_wave < TD_WAVES ) ? d_mom_dbg[L.iter_index & ( TD_ITERS - 1 )][td_wave] : nullptr;
+  int td_tile = 0;
+#endif
+  TD_STAMP( dbg, 0 );
   Pt cur = fetch( t );
+  TD_STAMP( dbg, 1 );
   for( ; t < t_end; t += stride )
   {
     const Pt nxt = fetch( t + stride );
@@ -1414,7 +1521,12 @@ __global__ __launch_bounds__( BLOCK ) void k_plain_moments( IcpLaunch L )
       moments_add( acc, w, px, py, pz, q4, n4 );
     }
     cur = nxt;
+#if RS_TAIL_DBG
+    if( td_tile < TD_TILES ) TD_STAMP( dbg, 2 + td_tile );
+    ++td_tile;
+#endif
   }
+  TD_STAMP( dbg, 13 );
   { const double v = wave_sums( acc, lane ); if( lane < ICP_NMOM ) red[wib][lane] = v; }
   __syncthreads();
   if( threadIdx.x < ICP_NMOM )
@@ -1423,6 +1535,10 @@ __global__ __launch_bounds__( BLOCK ) void k_plain_moments( IcpLaunch L )
     for( int w = 0; w < WAVES_PER_BLOCK; ++w ) v += red[w][threadIdx.x];
     L.mom_part[( (size_t)prob * ICP_NMOM + threadIdx.x ) * L.n_mom_blocks + blockIdx.x] = v;      // (moment-major, as k_chain_moments: L.n_mom_blocks == gridDim.x)
   }
+#if RS_TAIL_DBG
+  TD_STAMP( dbg, 14 );
+  if( dbg ) dbg[15] = (unsigned long long)td_tile;
+#endif
 }
 
 #define CH_M_LO ( 1 << 23 )
@@ -2594,7 +2710,7 @@ void launch_icp_plain_from_records( const IcpLaunch& L, const ChainBufs& B, hipS
 {
   ChainBufs Bq = B; Bq.refresh = 0;
   hipLaunchKernelGGL( k_chain_moments, dim3( B.n_blk * CH_QUARTERS, L.n_prob ), dim3( BLOCK ), 0, st, L, Bq );
-  hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, B.done );
+  launch_icp_update_wide( L, B.done, st );
 }
 
 // The same step from the searches' matches (L.rec == null in its search: no records written): k_plain_moments' partials, one per
@@ -2602,7 +2718,7 @@ void launch_icp_plain_from_records( const IcpLaunch& L, const ChainBufs& B, hipS
 void launch_icp_plain_from_matches( const IcpLaunch& L, const ChainBufs& B, hipStream_t st )
 {
   hipLaunchKernelGGL( k_plain_moments, dim3( L.n_mom_blocks, L.n_prob ), dim3( BLOCK ), 0, st, L );
-  hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, B.done );
+  launch_icp_update_wide( L, B.done, st );
 }
 
 void launch_icp_chain_centroids( const IcpLaunch& L, const ChainBufs& B, hipStream_t st )
@@ -2624,7 +2740,7 @@ void launch_icp_chain_centroids( const IcpLaunch& L, const ChainBufs& B, hipStre
     hipLaunchKernelGGL( k_chain_compose, dim3( B.n_blk, L.n_prob, CH_ROWS ), dim3( 3 * WAVE ), 0, st, L, B );
     hipLaunchKernelGGL( k_chain_walk_and_moments, dim3( CH_ROWS + B.n_blk * ( CH_QUARTERS + 1 ), L.n_prob ), dim3( BLOCK ), 0, st, L, B );
   }
-  hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, B.done );                // (centred on the chains' totals: L.exact_centroids)
+  launch_icp_update_wide( L, B.done, st );                // (centred on the chains' totals: L.exact_centroids)
 }
 
 // The same from the searches' records (L.rec: the grid chains' own inputs — what a scan the chains give up is run with): the fp64
@@ -2633,7 +2749,7 @@ void launch_icp_exact_centroids_from_records( const IcpLaunch& L, const ReplayBu
 {
   hipLaunchKernelGGL( k_chain_moments, dim3( C.n_blk * CH_QUARTERS, L.n_prob ), dim3( BLOCK ), 0, st, L, C );          // (L.n_mom_blocks == 4 C.n_blk)
   launch_replay_pass<2>( L, B, st );
-  hipLaunchKernelGGL( k_icp_update_wide, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, C.done );
+  launch_icp_update_wide( L, C.done, st );
 }
 int replay_segments( int n_source ) { return ( n_source + REPLAY_SEG - 1 ) / REPLAY_SEG; }
 int replay_superblocks( int n_source ) { return ( replay_segments( n_source ) + REPLAY_SUPER - 1 ) / REPLAY_SUPER; }

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Kernel A/B experiments: build librescan_hip_<tag>.so with extra -D flags and select it at run time with
 # RS_HIP_LIB=<path> (rescan_amd/capi.py).   usage: tools/variant.sh <tag> [-DNAME=VALUE ...]
+#   tools/variant.sh dbg -DRS_DBG=1            per-tile timers of the search kernels (RS_HIP_DEBUG_CYCLES)
+#   tools/variant.sh taildbg -DRS_TAIL_DBG=1   phase stamps of k_plain_moments / k_icp_update_wide, rs_hip_debug_tail_dump (csrc/rs_tail_dbg.h)
 set -e
 cd "$(dirname "$0")/../rescan_amd"
 tag=$1; shift
