@@ -90,6 +90,18 @@ int   rsd_alignment_scores( const rsd_vec3_t* obj_pos, const rsd_vec3_t* obj_nor
                             const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn,
                             const rsd_mat4_t* xforms, int32_t n_poses, float search_radius, int32_t max_n_neigh,
                             float* scores );
+/* mgs_propose_poses (apps/pose_proposal/pose_proposal.cpp:325-369) for the objects the caller names (it leaves the static ones
+ * out: rsdb_is_object_static), the whole cascade on the device (rs_hip_propose_poses).  Entry [o * n_levels + l] of obj_pos /
+ * obj_nor / n_obj = objects[o].shape->positions / normals / n_pts of level RSPC_N_LEVELS - 1 - l; scn_* = the scan's level 1;
+ * bbox_* = input_scan->bbox; the reference's constants: opts->search_grid_spacing, opts->search_grid_angle_delta, height 0,
+ * thresholds { 0.25f, 0.35f, 0.40f }, search_radius 0.1f, max_n_neigh 64.  counts[o] proposals of object o in
+ * xforms[o * capacity ..] / scores[o * capacity ..], in the reference's order, the ones marked -1 included.  More than
+ * `capacity` for an object: RS_HIP_E_CAPACITY (-4), counts hold what is needed, nothing else is written. */
+int   rsd_propose_poses( const rsd_vec3_t* const* obj_pos, const rsd_vec3_t* const* obj_nor, const int32_t* n_obj, int32_t n_objects,
+                         int32_t n_levels, const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn,
+                         const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float spacing, float angle_delta, float height,
+                         const float* thresholds, float search_radius, int32_t max_n_neigh, int32_t capacity,
+                         int32_t* counts, rsd_mat4_t* xforms, float* scores );
 /* isect_get_overlap_factor (lib/rs/intersect.h:309-368) of two placed shapes, bit for bit: *_lvl1 = shape->positions[1] (the
  * points that are rasterised), *_lvl3 = shape->positions[3] (the points whose boxes size the grid).  *overlap is written on
  * success only (0; < 0: an RS_HIP_E_* code, see rs_hip_overlap_factors). */

@@ -704,6 +704,66 @@ int rs_hip_relabel_walls_and_floors( const rs_hip_cloud_t* cloud, const float* c
  * loads.  Same counts.  form < 0 only reads.  Returns the previous form. */
 int32_t rs_hip_plane_votes_form( int32_t form );
 
+/* ---- pose proposals: the multi-resolution grid search (SURVEY.md §2 row 5, §3.2 "hot loop A") ---- */
+
+/* mgs_propose_poses (apps/pose_proposal/pose_proposal.cpp:325-369): a grid search over (cell x, cell z, yaw) with the objects'
+ * coarsest level, the survivors scored again with the finer ones.  The constants are the caller's, never the library's; the
+ * reference's are spacing 0.10f, angle_delta (float)( MSH_TWO_PI / 10.0f ), height 0, thresholds { 0.25f, 0.35f, 0.40f } for levels
+ * 4, 3, 2, radius 0.1f (the scene's level 1), max_n_neigh 64.  Static objects are the caller's to leave out (rsdb_is_object_static).
+ * Not covered: the distance-field gate (:223-227), which mgs_propose_poses never passes. */
+
+/* The host part alone; needs no device.  The tables of the grid, by the reference's loops as written (:203-222): ox / oz start at
+ * -spacing and are accumulated with fp32 += while < length + spacing, compared in fp32 (a length of 3.2 at spacing 0.1 gives 35
+ * steps, one more than the real numbers); the yaw angle starts at 0.0f and is accumulated in fp32 while < the double 6.2831853072;
+ * yaw[16 k ..] = msh_rotate( identity, angle_k, (0,1,0) ), column-major, with the host libm's sinf / cosf.  Two passes: the
+ * counts are always written; a table that is NULL is not asked for; a table shorter than its count (cap_*) gives
+ * RS_HIP_E_CAPACITY and no table is written.  RS_HIP_E_ARG: a box that is not finite, spacing or angle_delta not > 0, or a step so
+ * small that its fp32 counter would not advance (the reference's loop would not end); RS_HIP_E_CAPACITY: more than 2^20 steps. */
+int rs_hip_pose_grid_plan( const float bbox_min[3], const float bbox_max[3], float spacing, float angle_delta,
+                           int32_t* n_x, int32_t* n_z, int32_t* n_yaw,
+                           float* ox /* may be NULL */, int32_t cap_x, float* oz /* may be NULL */, int32_t cap_z,
+                           float* yaw /* may be NULL, 16 per step */, int32_t cap_yaw );
+
+/* What a search did, for tests and diagnostics; each array may be NULL.  Entry [o * n_levels + l]: n_scored = the poses of object o
+ * scored at level l (level 0: the whole grid; later: the proposals whose score was > 0.0f), n_kept = its proposals with a score
+ * > 0.0f after the level.  n_proposed[o] = the length of the object's proposal storage (it never shrinks, :292). */
+typedef struct rs_hip_propose_trace
+{
+  int32_t* n_scored; int32_t* n_kept;    /* n_objects * n_levels */
+  int32_t* n_proposed;                   /* n_objects */
+} rs_hip_propose_trace_t;
+
+/* The search for n_objects objects at once.  objects[o * n_levels + l]: object o's cloud of level l, coarsest first (the reference:
+ * levels 4, 3, 2), each with normals; n_levels 1..4.  scene: the cloud that is searched (the reference: level 1), bbox_*: the
+ * scan's bounding box, whose min is the grid's origin.  Kept as the reference has it:
+ *   level 0      the pose of (cell i, j; yaw k) is yaw[k] with col[3] = ( min.x + ox[i], height, min.z + oz[j], 1 ), cells x-outer and
+ *                z-inner; per cell the best score starts at 0 and is replaced by strict > in yaw order (the first of equals wins, a
+ *                NaN never); the cell proposes where best > thresholds[0], in cell order
+ *   level l      only proposals with score > 0.0f are scored again and become score > thresholds[l] ? score : -1.0f
+ *   final lists  every proposal with fabsf( score ) > 0.000001f, in order — the ones marked -1 included, which the reference hands
+ *                to its non-maximum suppression
+ *   an object level of 0 points scores NaN: at level 0 nothing is proposed, later its proposals become -1
+ * counts[o] = the length of object o's list, poses[( o * capacity + i ) * 16 ..] and scores[o * capacity + i] its entries.  An
+ * object with more than `capacity` entries: RS_HIP_E_CAPACITY, counts hold what is needed, poses and scores are not written.
+ * The poses are made on the device from the planner's tables and scored by the launches of rs_hip_alignment_scores (more than
+ * 65 535 in chunks); between levels only counts come to the host, n_levels waits per call whatever n_objects is. */
+int rs_hip_propose_poses( const rs_hip_cloud_t* const* objects, int32_t n_objects, int32_t n_levels, const rs_hip_cloud_t* scene,
+                          const float bbox_min[3], const float bbox_max[3], float spacing, float angle_delta, float height,
+                          const float* thresholds /* n_levels */, float radius, int32_t max_n_neigh, int32_t capacity,
+                          int32_t* counts /* n_objects */, float* poses /* n_objects * capacity * 16 */,
+                          float* scores /* n_objects * capacity */, rs_hip_propose_trace_t* trace /* may be NULL */ );
+
+/* The two judging stages on host arrays (the device kernels of the search, run on uploaded scores).
+ * rs_hip_cell_best: scores[c * n_yaw + k]; best_yaw[c] = the winning k (-1: no score > 0), best_score[c] (0 then),
+ * keep[c] = the cell's slot in the proposal list — the number of proposing cells before it — or -1 where best_score[c] is not
+ * > threshold.
+ * rs_hip_verify_marks: out[i] = old[i] > 0.0f ? ( new[i] > threshold ? new[i] : -1.0f ) : old[i]; out may be old_scores. */
+int rs_hip_cell_best( const float* scores, int32_t n_cells, int32_t n_yaw, float threshold,
+                      int32_t* best_yaw, float* best_score, int32_t* keep );
+int rs_hip_verify_marks( const float* old_scores, const float* new_scores, int32_t n, float threshold, float* out );
+/* Frees the search's buffers of the calling thread (they are kept between calls otherwise). */
+int rs_hip_propose_release( void );
+
 /* ---- host-side helpers shared by the drop-in shim (exact reference arithmetic) ------- */
 
 /* msh_mat4_inverse / msh_mat4_mul (lib/msh/msh_vec_math.h:1818-1905, 1441-1476) */

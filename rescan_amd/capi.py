@@ -122,6 +122,13 @@ SIGNATURES = {
     "rs_hip_gather_plane_inliers": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "rs_hip_relabel_walls_and_floors": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
     "rs_hip_plane_votes_form": (C.c_int32, [C.c_int32]),
+    "rs_hip_pose_grid_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "rs_hip_propose_poses": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                       C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_cell_best": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_verify_marks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
+    "rs_hip_propose_release": (C.c_int, []),
     "rs_hip_overlap_factors": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float,
                                          C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "rs_hip_nms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
@@ -142,6 +149,11 @@ class RescanHipError(RuntimeError):
 class IsectShape(C.Structure):
     """rs_hip_isect_shape_t: (boundary cloud, extent cloud) of one object."""
     _fields_ = [("boundary", C.c_void_p), ("extent", C.c_void_p)]
+
+
+class ProposeTrace(C.Structure):
+    """rs_hip_propose_trace_t"""
+    _fields_ = [("n_scored", C.c_void_p), ("n_kept", C.c_void_p), ("n_proposed", C.c_void_p)]
 
 
 class Placement(C.Structure):
@@ -791,6 +803,75 @@ def alignment_scores(obj, scene, poses, radius=0.1, max_n_neigh=64):
     _check(load().rs_hip_alignment_scores(obj.handle, scene.handle, poses, len(poses), float(radius),
                                           int(max_n_neigh), out))
     return out
+
+
+def pose_grid_plan(bbox_min, bbox_max, spacing, angle_delta, tables=True):
+    """The host part of the pose search (rs_hip_pose_grid_plan; no device needed): (ox, oz, yaw) — the cell offsets along x and z
+    and one 16-float rotation per yaw step, by the reference's float loops as written; tables=False: the three counts only."""
+    lo, hi = _f32(bbox_min).ravel(), _f32(bbox_max).ravel()
+    nx, nz, ny = C.c_int32(), C.c_int32(), C.c_int32()
+    lib = load()
+    _check(lib.rs_hip_pose_grid_plan(lo.ctypes.data, hi.ctypes.data, float(spacing), float(angle_delta), C.byref(nx), C.byref(nz), C.byref(ny),
+                                     None, 0, None, 0, None, 0))
+    if not tables:
+        return nx.value, nz.value, ny.value
+    ox, oz, yaw = np.zeros(nx.value, np.float32), np.zeros(nz.value, np.float32), np.zeros((ny.value, 16), np.float32)
+    _check(lib.rs_hip_pose_grid_plan(lo.ctypes.data, hi.ctypes.data, float(spacing), float(angle_delta), C.byref(nx), C.byref(nz), C.byref(ny),
+                                     ox.ctypes.data, len(ox), oz.ctypes.data, len(oz), yaw.ctypes.data, len(yaw)))
+    return ox, oz, yaw
+
+
+def propose_poses(objects, scene, bbox_min, bbox_max, spacing, angle_delta, height, thresholds, radius, max_n_neigh, capacity=None,
+                  trace=False):
+    """mgs_propose_poses on the device (rs_hip_propose_poses).  objects: one sequence of level clouds per object, coarsest first,
+    all of the same length as thresholds; scene: the cloud that is searched.  Returns a list of (poses (n, 16), scores (n,)) per
+    object, with trace a dict of n_scored / n_kept (n_objects, n_levels) and n_proposed (n_objects) as well.  capacity (entries
+    per object) defaults to the number of cells, which no list can exceed; a smaller one that does not suffice raises."""
+    thresholds = _f32(thresholds).ravel()
+    n_levels, n_obj = len(thresholds), len(objects)
+    if any(len(o) != n_levels for o in objects):
+        raise ValueError("propose_poses: every object needs one cloud per threshold")
+    lo, hi = _f32(bbox_min).ravel(), _f32(bbox_max).ravel()
+    if capacity is None:
+        nx, nz, _ = pose_grid_plan(lo, hi, spacing, angle_delta, tables=False)
+        capacity = nx * nz
+    handles = (C.c_void_p * max(1, n_obj * n_levels))(*[c.handle for o in objects for c in o])
+    counts = np.zeros(max(1, n_obj), np.int32)
+    poses, scores = np.zeros((max(1, n_obj), capacity, 16), np.float32), np.zeros((max(1, n_obj), capacity), np.float32)
+    tr, t = None, None
+    if trace:
+        t = dict(n_scored=np.zeros((n_obj, n_levels), np.int32), n_kept=np.zeros((n_obj, n_levels), np.int32), n_proposed=np.zeros(n_obj, np.int32))
+        tr = ProposeTrace(t["n_scored"].ctypes.data, t["n_kept"].ctypes.data, t["n_proposed"].ctypes.data)
+    _check(load().rs_hip_propose_poses(handles, n_obj, n_levels, scene.handle, lo.ctypes.data, hi.ctypes.data, float(spacing), float(angle_delta),
+                                       float(height), thresholds.ctypes.data, float(radius), int(max_n_neigh), int(capacity), counts.ctypes.data,
+                                       poses.ctypes.data, scores.ctypes.data, C.byref(tr) if trace else None))
+    out = [(poses[o, :counts[o]].copy(), scores[o, :counts[o]].copy()) for o in range(n_obj)]
+    return (out, t) if trace else out
+
+
+def cell_best(scores, threshold):
+    """The per-cell judgement of the grid search on host scores (n_cells, n_yaw) (rs_hip_cell_best): best_yaw (-1: none), best_score
+    and keep — the cell's slot in the proposal list, -1 where it proposes nothing."""
+    scores = _f32(scores)
+    n_cells, n_yaw = scores.shape
+    by, bs, keep = np.zeros(n_cells, np.int32), np.zeros(n_cells, np.float32), np.zeros(n_cells, np.int32)
+    _check(load().rs_hip_cell_best(scores.ctypes.data, n_cells, n_yaw, float(threshold), by.ctypes.data, bs.ctypes.data, keep.ctypes.data))
+    return by, bs, keep
+
+
+def verify_marks(old_scores, new_scores, threshold):
+    """A verification level's marks on host scores (rs_hip_verify_marks): old > 0 ? (new > threshold ? new : -1) : old."""
+    old, new = _f32(old_scores).ravel(), _f32(new_scores).ravel()
+    if len(old) != len(new):
+        raise ValueError("verify_marks: one new score per old one")
+    out = np.zeros(len(old), np.float32)
+    _check(load().rs_hip_verify_marks(old.ctypes.data, new.ctypes.data, len(old), float(threshold), out.ctypes.data))
+    return out
+
+
+def propose_release():
+    """Frees the pose search's buffers of the calling thread."""
+    _check(load().rs_hip_propose_release())
 
 
 def _placements(poses, objects, radii):

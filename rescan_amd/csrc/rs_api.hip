@@ -1870,30 +1870,27 @@ int64_t rs_hip_score_scene_space_from( int64_t n_queries )
   return prev;
 }
 
-int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t* scene,
-                             const float* poses, int32_t n_poses, float radius, int32_t max_n_neigh,
-                             float* scores )
+// The launches of a batch whose poses are on the device already and whose scores stay there (the calling thread's stream; no
+// copy, no wait): rs_hip_alignment_scores below is this between an upload and a read-back, rs_propose.hip calls it per object and
+// level.  Where queries can fall — the scene-space route's lattice — comes from the poses where the host has them (h_poses), else
+// from query_box (lo[3], hi[3]; null: the scene's box).  object->n >= 1, n_poses >= 1.
+static int score_poses_device( const rs_hip_cloud_t* object, const rs_hip_cloud_t* scene, const float* d_poses, const float* h_poses,
+                               const float* query_box, int32_t n_poses, float radius, int32_t max_n_neigh, float* d_scores,
+                               unsigned long long* hist )
 {
-  int rc = ensure_ready(); if( rc ) return rc;
-  if( !object || !scene || !object->has_nor || !scene->has_nor || !poses || !scores || n_poses < 0 || max_n_neigh <= 0 )
-  { set_err( "alignment_scores: bad arguments" ); return RS_HIP_E_ARG; }
-  if( n_poses == 0 ) return RS_HIP_OK;
-  if( object->n == 0 ) { for( int p = 0; p < n_poses; ++p ) scores[p] = NAN; return RS_HIP_OK; }   // 0/0, pose_proposal.cpp:156
+  int rc;
+  const float* poses = h_poses;
   const int n_tiles = object->qview.n_tiles;
-  if( ( rc = g_ws.poses.ensure( (size_t)n_poses * 64 ) ) || ( rc = g_ws.score_part.ensure( (size_t)n_poses * n_tiles * 8 ) ) ||
-      ( rc = g_ws.scores.ensure( (size_t)n_poses * 4 ) ) ||
+  if( ( rc = g_ws.score_part.ensure( (size_t)n_poses * n_tiles * 8 ) ) ||
       ( rc = g_ws.queue.ensure( (size_t)std::min( n_poses, 65535 ) * n_tiles * 4 ) ) || ( rc = g_ws.queue_count.ensure( 4 ) ) )
     return rc;
-  HIP_TRY( hipMemcpyAsync( g_ws.poses.p, poses, (size_t)n_poses * 64, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
   ScoreLaunch L{};
   L.scene = scene->view; L.scene.evals = g_prof ? g_evals : nullptr; L.obj = object->qview;
-  L.poses = g_ws.poses.as<float>(); L.radius_sq = radius_sq_of( radius ); L.gate_tmin = score_gate_threshold();
-  L.K = max_n_neigh; L.sigma = (double)radius; L.part = g_ws.score_part.as<double>(); L.scores = g_ws.scores.as<float>();
+  L.poses = d_poses; L.radius_sq = radius_sq_of( radius ); L.gate_tmin = score_gate_threshold();
+  L.K = max_n_neigh; L.sigma = (double)radius; L.part = g_ws.score_part.as<double>(); L.scores = d_scores;
   L.queue = g_ws.queue.as<int>(); L.queue_count = g_ws.queue_count.as<int>();
   L.solo_stages = handoff_threshold( (long long)n_tiles * n_poses );
-  L.hist = nullptr;
-  thread_local DevBuf histbuf;
-  if( RS_DBG && getenv( "RS_HIP_SCORE_HIST" ) && !histbuf.ensure( 7 * 65 * 8 ) ) { (void)hipMemsetAsync( histbuf.p, 0, 7 * 65 * 8, g_stream ); L.hist = histbuf.as<unsigned long long>(); }
+  L.hist = hist;
   // Scene-space route (rs_score.hip: k_score_scene) for batches on a cell grid that are worth a sort: every query keyed by the
   // scene-aligned block it lands in.  RS_HIP_SCORE_SCENE=0 turns it off, RS_HIP_SCORE_SCENE_MIN sets the batch size it starts at.
   static const int scene_route = getenv( "RS_HIP_SCORE_SCENE" ) ? atoi( getenv( "RS_HIP_SCORE_SCENE" ) ) : 1;
@@ -1914,7 +1911,15 @@ int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t*
     // ... and the parent lattice only spans where queries CAN fall: the object's box under every pose, cut to that box (fewer key
     // bits: a radix pass less).  The object's own grid spans its bounding box; a brute-layout object falls back to the scene's box.
     const GridView& og = object->view;
-    if( og.inv_cell > 0.0f )
+    if( !poses && query_box )
+    {
+      for( int a = 0; a < 3; ++a )
+      {
+        lo[a] = std::max( lo[a], query_box[a] ); hi[a] = std::min( hi[a], query_box[3 + a] );
+        if( hi[a] < lo[a] ) hi[a] = lo[a];
+      }
+    }
+    else if( poses && og.inv_cell > 0.0f )
     {
       float qlo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, qhi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
       const float omin[3] = { og.minx, og.miny, og.minz }, omax[3] = { og.minx + og.w * og.cell, og.miny + og.h * og.cell, og.minz + og.d * og.cell };
@@ -1988,12 +1993,30 @@ int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t*
     ProfScope ps( "nn_score" );
     launch_score( Lp, g_stream );
   }
+  return RS_HIP_OK;
+}
+
+int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t* scene,
+                             const float* poses, int32_t n_poses, float radius, int32_t max_n_neigh,
+                             float* scores )
+{
+  int rc = ensure_ready(); if( rc ) return rc;
+  if( !object || !scene || !object->has_nor || !scene->has_nor || !poses || !scores || n_poses < 0 || max_n_neigh <= 0 )
+  { set_err( "alignment_scores: bad arguments" ); return RS_HIP_E_ARG; }
+  if( n_poses == 0 ) return RS_HIP_OK;
+  if( object->n == 0 ) { for( int p = 0; p < n_poses; ++p ) scores[p] = NAN; return RS_HIP_OK; }   // 0/0, pose_proposal.cpp:156
+  if( ( rc = g_ws.poses.ensure( (size_t)n_poses * 64 ) ) || ( rc = g_ws.scores.ensure( (size_t)n_poses * 4 ) ) ) return rc;
+  HIP_TRY( hipMemcpyAsync( g_ws.poses.p, poses, (size_t)n_poses * 64, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
+  unsigned long long* hist = nullptr;
+  thread_local DevBuf histbuf;
+  if( RS_DBG && getenv( "RS_HIP_SCORE_HIST" ) && !histbuf.ensure( 7 * 65 * 8 ) ) { (void)hipMemsetAsync( histbuf.p, 0, 7 * 65 * 8, g_stream ); hist = histbuf.as<unsigned long long>(); }
+  if( ( rc = score_poses_device( object, scene, g_ws.poses.as<float>(), poses, nullptr, n_poses, radius, max_n_neigh, g_ws.scores.as<float>(), hist ) ) ) return rc;
   HIP_TRY( hipMemcpyAsync( scores, g_ws.scores.p, (size_t)n_poses * 4, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
   HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
-  if( L.hist && n_poses >= 256 )
+  if( hist && n_poses >= 256 )
   {
     std::vector<unsigned long long> h( 7 * 65 );
-    (void)hipMemcpy( h.data(), L.hist, h.size() * 8, hipMemcpyDeviceToHost );
+    (void)hipMemcpy( h.data(), hist, h.size() * 8, hipMemcpyDeviceToHost );
     unsigned long long all = 0; for( size_t k = 0; k < 6 * 65; ++k ) all += h[k];
     {
       unsigned long long ns = 0, nl = 0, b[5] = { 0, 0, 0, 0, 0 };
@@ -2767,6 +2790,13 @@ rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float ce
 {
   return cloud_create_impl( g_ws.lvl_pos.as<float>(), with_nor ? g_ws.lvl_nor.as<float>() : nullptr, n, cell_size, true );
 }
+int api_score_poses_device( const rs_hip_cloud* object, const rs_hip_cloud* scene, const float* d_poses, const float* query_box,
+                            int32_t n_poses, float radius, int32_t max_n_neigh, float* d_scores )
+{
+  if( !object->has_nor || !scene->has_nor || object->n <= 0 || n_poses <= 0 ) { set_err( "score_poses_device: bad arguments" ); return RS_HIP_E_ARG; }
+  return score_poses_device( object, scene, d_poses, nullptr, query_box, n_poses, radius, max_n_neigh, d_scores, nullptr );
+}
+bool api_cloud_has_normals( const rs_hip_cloud* c ) { return c->has_nor; }
 CloudPoints api_cloud_points( const rs_hip_cloud* c )
 {
   return CloudPoints{ c->d_qpos, c->has_nor ? c->d_qnor : nullptr, c->d_qby_orig, c->n };

@@ -752,6 +752,29 @@ int rsd_alignment_scores( const rsd_vec3_t* obj_pos, const rsd_vec3_t* obj_nor, 
   return rc;
 }
 
+// mgs_propose_poses on host arrays: obj_pos[o * n_levels + l] / obj_nor / n_obj = objects[o].shape->positions / normals / n_pts
+// of level l's cloud, coarsest first (the reference: levels 4, 3, 2); the static objects are the caller's to leave out
+int rsd_propose_poses( const rsd_vec3_t* const* obj_pos, const rsd_vec3_t* const* obj_nor, const int32_t* n_obj, int32_t n_objects, int32_t n_levels,
+                       const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn, const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max,
+                       float spacing, float angle_delta, float height, const float* thresholds, float search_radius, int32_t max_n_neigh,
+                       int32_t capacity, int32_t* counts, rsd_mat4_t* xforms, float* scores )
+{
+  if( n_objects < 0 || n_levels < 1 || !bbox_min || !bbox_max || ( n_objects > 0 && ( !obj_pos || !obj_nor || !n_obj ) ) ) return RS_HIP_E_ARG;
+  const CloudRef scn = cached_cloud( scn_pos, scn_nor, n_scn, -1.0f );
+  if( !scn ) return RS_HIP_E_RUNTIME;
+  std::vector<CloudRef> held; std::vector<const rs_hip_cloud_t*> clouds;
+  for( int64_t k = 0; k < (int64_t)n_objects * n_levels; ++k )
+  {
+    held.push_back( cached_cloud( obj_pos[k], obj_nor[k], n_obj[k], -1.0f ) );
+    if( !held.back() ) return RS_HIP_E_RUNTIME;
+    clouds.push_back( held.back().get() );
+  }
+  const int rc = rs_hip_propose_poses( clouds.data(), n_objects, n_levels, scn.get(), (const float*)bbox_min, (const float*)bbox_max, spacing, angle_delta,
+                                       height, thresholds, search_radius, max_n_neigh, capacity, counts, (float*)xforms, scores, nullptr );
+  if( rc && rc != RS_HIP_E_CAPACITY ) complain( "propose_poses" );
+  return rc;
+}
+
 float rsd_alignment_score( const rsd_vec3_t* obj_pos, const rsd_vec3_t* obj_nor, int32_t n_obj,
                            const rsd_vec3_t* scn_pos, const rsd_vec3_t* scn_nor, int32_t n_scn,
                            rsd_mat4_t xform, float search_radius, int32_t max_n_neigh )

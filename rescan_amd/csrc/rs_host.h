@@ -1,5 +1,5 @@
 // Host runtime shared by the translation units with entry points of their own (rs_knn.hip, rs_isect.hip, rs_arrange.hip,
-// rs_mesh.hip, rs_fuse.hip, rs_planes.hip): what they need from rs_api.hip, a growable buffer, the failure path, a profiling
+// rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip): what they need from rs_api.hip, a growable buffer, the failure path, a profiling
 // span and the grid size of a launch.  Host only: no kernel file needs it.
 #pragma once
 #include "../../include/rescan_hip.h"
@@ -24,6 +24,12 @@ struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n,
 // original index to its slot there; nor is null for a cloud without normals
 struct CloudPoints { const float4* qpos; const float4* qnor; const int* by_orig; int n; };
 CloudPoints     api_cloud_points( const struct ::rs_hip_cloud* c );
+bool            api_cloud_has_normals( const struct ::rs_hip_cloud* c );
+// rs_hip_alignment_scores without its upload and read-back, for a caller in another unit (rs_propose.hip): n_poses >= 1 device poses
+// of an object of >= 1 points scored into device scores, queued on the calling thread's stream, booked under nn_score.  query_box
+// (lo[3], hi[3]; may be null): where the object's points can fall under these poses, which the scene-space route's lattice is cut to.
+int             api_score_poses_device( const struct ::rs_hip_cloud* object, const struct ::rs_hip_cloud* scene, const float* d_poses,
+                                        const float* query_box, int32_t n_poses, float radius, int32_t max_n_neigh, float* d_scores );
 
 // A device (or pinned host) buffer grown on demand and kept between calls, one per member of a unit's thread_local workspace.
 // NO destructor on purpose: a thread_local's destructor of the main thread runs at process exit, where the HIP runtime may
