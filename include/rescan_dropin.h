@@ -157,6 +157,12 @@ int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, cons
                               rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_vec3_t* out_col, float* out_radii,
                               int32_t* out_class, int32_t* out_instance );
 
+/* rs_pointcloud__compute_normals (lib/rs/rs_pointcloud.h:556-596) on pc->positions[0] and faces_ind: pc->normals[0], bit for bit
+ * (where the reference's value is NaN, a NaN).  The loader's own pass (:743-751) stays where it is.  Returns 0, or a negative
+ * RS_HIP_E_* code with nothing written: no face, an index outside [0, n), counts above INT32_MAX (include/rescan_hip.h:
+ * rs_hip_vertex_normals). */
+int32_t rsd_compute_normals( const rsd_vec3_t* positions, int64_t n, const int32_t* faces_ind, int64_t n_faces, rsd_vec3_t* normals );
+
 /* The body of rsdu_augment_database's `if( extracted_shape )` block (apps/segment_transfer/database_update.cpp:58-90) for one
  * placement, extraction included: the points of input_scan's level 1 that carry uidx, aligned to cur_shape's level 0 by icp_align
  * ( .., 0.05, msh_deg2rad( 10 ) ) from inverse( pose ) unless is_static, transformed, merged with cur_shape and shuffled — the level-0

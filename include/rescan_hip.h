@@ -442,6 +442,33 @@ int rs_hip_uniform_resample( const float* pos, const float* nor, const float* co
 rs_hip_cloud_t* rs_hip_cloud_create_resampled( const float* pos, const float* nor, int64_t n_vertices,
                                                const int32_t* faces, int64_t n_faces, float cell_size, int64_t* n_samples );
 
+/* The step before the resampler, for a mesh that comes without normals (surface reconstruction hands such meshes back):
+ * rs_pointcloud__compute_normals (lib/rs/rs_pointcloud.h:556-596), which rs_pointcloud__load_ply calls for a PLY with faces and
+ * no normals (:716-723); loader_pass != 0 adds the loader's own pass over the result (:743-751).  Bit for bit, all fp32:
+ *   face normal   cross( p2 - p1, p3 - p1 ), not normalised (msh_vec_math.h:974-979)
+ *   vertex chain  faces in ascending index, corners 1, 2, 3: n[v] = lerp( n[v], normal, 1.0f / ( (float)counts[v] + 1.0f ) )
+ *                 (msh_vec3_lerp: u = 1.0f - t, t * b + u * a); counts advance after the face's three corners, so a face that
+ *                 names a vertex twice or three times applies the lerp that often with one t and adds 2 or 3 to the count
+ *   finish        norm > 0 -> n * ( 1.0f / sqrtf( sum ) ); otherwise (0, 1, 0): a vertex no face names, a sum that cancels to
+ *                 zero, a NaN (it fails the compare).  An infinite norm passes and normalises to NaN, as in the reference
+ *   loader pass   msh_vec3_normalize once more; a normal with a NaN component becomes (0, 0, 0)
+ * Where the reference's value is NaN the device's is NaN too; its sign and payload are the multiplier's.
+ * Host pointers; out_nor 3 * n_vertices floats; counts (may be NULL) n_vertices: the corners that name each vertex.
+ *
+ * Refusals, each RS_HIP_E_ARG and decided before a device is touched, with nothing written: a NULL pos, faces or out_nor;
+ * n_vertices <= 0; n_faces <= 0 (the reference then leaves malloc'ed memory unwritten, :718-722); a vertex index outside
+ * [0, n_vertices) (the reference reads out of bounds); 3 * n_faces or n_vertices above INT32_MAX.  Coordinates that are not
+ * finite are NOT refused: the reference's function is defined on them. */
+int rs_hip_vertex_normals( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                           int32_t loader_pass, float* out_nor, int32_t* counts /* may be NULL */ );
+
+/* A mesh as a PLY without normals holds it -> the indexed level-0 cloud, without leaving the device: the normals above with
+ * the loader pass, written into the vertex records the sampler reads, then exactly what rs_hip_cloud_create_resampled does
+ * with them.  Refuses what rs_hip_vertex_normals refuses and what the resampler refuses.  n_samples may be NULL.  NULL on
+ * failure. */
+rs_hip_cloud_t* rs_hip_cloud_create_from_mesh( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                                               float cell_size, int64_t* n_samples );
+
 /* ---- model fusion: the row that closes a timestep ------------------------- */
 
 /* rsdu_augment_database (apps/segment_transfer/database_update.cpp:22-91) for one placement: the scan's points that carry

@@ -107,6 +107,8 @@ SIGNATURES = {
     "rs_hip_resample_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "rs_hip_uniform_resample": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7),
     "rs_hip_cloud_create_resampled": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.POINTER(C.c_int64)]),
+    "rs_hip_vertex_normals": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rs_hip_cloud_create_from_mesh": (C.c_void_p, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.POINTER(C.c_int64)]),
     "rs_hip_shuffle_plan": (C.c_int, [C.c_int64, C.c_uint32, C.c_void_p]),
     "rs_hip_shuffle_permutation": (C.c_int, [C.c_int64, C.c_uint32, C.c_void_p]),
     "rs_hip_select_by_ids": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int64)]),
@@ -297,6 +299,22 @@ class Cloud:
         return self
 
     @classmethod
+    def from_mesh(cls, pos, faces, cell_size=-1.0):
+        """The level-0 cloud of a mesh that comes without normals (rs_hip_cloud_create_from_mesh): vertex normals from the faces
+        with the loader's pass (vertex_normals(.., loader_pass=True)), then what resampled() does with them, all on the device."""
+        lib = load()
+        pos = _f32(pos).reshape(-1, 3); faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        n = C.c_int64()
+        h = lib.rs_hip_cloud_create_from_mesh(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces), float(cell_size), C.byref(n))
+        if not h:
+            raise RescanHipError("rs_hip_cloud_create_from_mesh failed: " + lib.rs_hip_last_error().decode())
+        self = cls.__new__(cls)
+        self.handle = h; self.n = n.value
+        self._pos = np.zeros((self.n, 3), np.float32); self._nor = np.zeros((self.n, 3), np.float32)
+        _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, self._nor.ctypes.data))
+        return self
+
+    @classmethod
     def fused(cls, scan, scan_instance_ids, uidx, model, pose, refine=True, max_dist=0.05, max_angle=np.float32(10.0 * 0.005555555556 * np.pi),
               cell_size=-1.0):
         """One placement of rsdu_augment_database on the device (rs_hip_cloud_create_fused): the scan's points with instance id
@@ -369,6 +387,17 @@ def resample_plan(pos, faces, table=True):
     _check(load().rs_hip_resample_plan(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces), C.byref(n), C.byref(total),
                                        prob.ctypes.data if table else None, alias.ctypes.data if table else None))
     return n.value, total.value, prob, alias
+
+
+def vertex_normals(pos, faces, loader_pass=False, counts=False):
+    """rs_pointcloud__compute_normals on the device (rs_hip_vertex_normals): the (n, 3) vertex normals of a mesh from its faces;
+    loader_pass adds rs_pointcloud__load_ply's pass over them.  counts: also the number of corners that name each vertex."""
+    pos = _f32(pos).reshape(-1, 3); faces = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    nor = np.zeros((len(pos), 3), np.float32)
+    cnt = np.zeros(len(pos), np.int32) if counts else None
+    _check(load().rs_hip_vertex_normals(pos.ctypes.data, len(pos), faces.ctypes.data, len(faces), int(bool(loader_pass)), nor.ctypes.data,
+                                        cnt.ctypes.data if counts else None))
+    return (nor, cnt) if counts else nor
 
 
 def uniform_resample(pos, faces, nor=None, col=None, radii=None, class_ids=None, instance_ids=None, first=0, count=None):

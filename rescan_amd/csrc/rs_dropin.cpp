@@ -909,6 +909,13 @@ int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, cons
   return n_samples;
 }
 
+int32_t rsd_compute_normals( const rsd_vec3_t* positions, int64_t n, const int32_t* faces_ind, int64_t n_faces, rsd_vec3_t* normals )
+{
+  const int rc = rs_hip_vertex_normals( (const float*)positions, n, faces_ind, n_faces, 0, (float*)normals, nullptr );
+  if( rc ) complain( "compute_normals" );
+  return rc;
+}
+
 int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_nor, const rsd_vec3_t* scan_col, const float* scan_radii,
                            const float* scan_qual, const int32_t* scan_class, const int32_t* scan_instance, int32_t n_scan,
                            const rsd_vec3_t* model_pos, const rsd_vec3_t* model_nor, const rsd_vec3_t* model_col, const float* model_radii,

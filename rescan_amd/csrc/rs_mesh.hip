@@ -20,10 +20,23 @@
 //                            lane's result depends on the launch geometry or on the window.
 // The fp32 arithmetic matches the reference's because the library is built with -ffp-contract=off and hipcc's default
 // correctly rounded fp32 divide and square root.
+//
+// The step before it, for a mesh that comes without normals: rs_pointcloud__compute_normals (lib/rs/rs_pointcloud.h:556-596) and the
+// loader's pass over its result (:743-751), bit for bit — rs_hip_vertex_normals, rs_hip_cloud_create_from_mesh.  A vertex normal is a
+// running mean over the faces that name the vertex, taken in face order: one vertex's chain is sequential, the chains of different
+// vertices are independent.
+//   k_face_cross     one lane per face: the unnormalised cross product, once, as a 16-byte record; and the face's three corners as
+//                    (vertex, 3 face + corner) pairs.
+//   stable sort      of the pairs by vertex over the bits n_vertices - 1 needs (hipCUB's radix sort, rs_build.hip): a vertex's corners
+//                    become one span, in ascending corner id, i.e. in the reference's order.  No atomic decides an order.
+//   k_span_start     where each vertex's span starts.
+//   k_vertex_chain   one lane per vertex walks its span: t once per face from the count before it, the lerp once per corner, then
+//                    the finish (:586-592) and, where asked, the loader's pass.  It writes where k_mesh_sample reads.
 #include "rs_host.h"
 #include "rs_mesh.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstring>
 #include <vector>
 
@@ -130,13 +143,94 @@ __global__ __launch_bounds__( MESH_BLOCK ) void k_mesh_sample( MeshSampleArgs A 
   if( A.out_face ) A.out_face[o] = face;
 }
 
+// ---- vertex normals from faces (rs_pointcloud__compute_normals, lib/rs/rs_pointcloud.h:556-596) ---------------------------------
+
+struct NormalArgs
+{
+  const float* pos; int32_t pos_stride;        // vertex v's position: pos + v * pos_stride (floats): 3 for a plain array, 12 for MeshVertex records
+  float* nor; int32_t nor_stride;              // ... and its normal, likewise
+  const int32_t* faces; int32_t n_vertices, n_faces, loader_pass;
+  float4* face_nor;                            // n_faces
+  uint32_t *key, *val;                         // 3 n_faces each: the corner list before the sort ...
+  const uint32_t *skey, *sval;                 // ... and after
+  int32_t* start;                              // n_vertices: the first entry of a vertex's span, -1 where no face names it
+  int32_t* counts;                             // n_vertices or null
+};
+
+__global__ __launch_bounds__( MESH_BLOCK ) void k_face_cross( NormalArgs A )
+{
+  const int32_t f = (int32_t)( blockIdx.x * MESH_BLOCK + threadIdx.x );
+  if( f >= A.n_faces ) return;
+  const int32_t i1 = A.faces[3 * (size_t)f], i2 = A.faces[3 * (size_t)f + 1], i3 = A.faces[3 * (size_t)f + 2];
+  const float* p1 = A.pos + (size_t)i1 * A.pos_stride, *p2 = A.pos + (size_t)i2 * A.pos_stride, *p3 = A.pos + (size_t)i3 * A.pos_stride;
+  const float ax = p2[0] - p1[0], ay = p2[1] - p1[1], az = p2[2] - p1[2];
+  const float bx = p3[0] - p1[0], by = p3[1] - p1[1], bz = p3[2] - p1[2];
+  A.face_nor[f] = make_float4( ay * bz - az * by, az * bx - ax * bz, ax * by - ay * bx, 0.0f );      // msh_vec3_cross, msh_vec_math.h:974-979
+  const uint32_t c = 3u * (uint32_t)f;
+  A.key[c] = (uint32_t)i1; A.key[c + 1] = (uint32_t)i2; A.key[c + 2] = (uint32_t)i3;
+  A.val[c] = c; A.val[c + 1] = c + 1; A.val[c + 2] = c + 2;
+}
+
+__global__ __launch_bounds__( MESH_BLOCK ) void k_span_start( NormalArgs A )
+{
+  const int64_t j = (int64_t)blockIdx.x * MESH_BLOCK + threadIdx.x;
+  if( j >= 3 * (int64_t)A.n_faces ) return;
+  const uint32_t v = A.skey[j];
+  if( j == 0 || A.skey[j - 1] != v ) A.start[v] = (int32_t)j;
+}
+
+__global__ __launch_bounds__( MESH_BLOCK ) void k_vertex_chain( NormalArgs A )
+{
+  const int32_t v = (int32_t)( blockIdx.x * MESH_BLOCK + threadIdx.x );
+  if( v >= A.n_vertices ) return;
+  const int64_t n_corners = 3 * (int64_t)A.n_faces;
+  float x = 0.0f, y = 0.0f, z = 0.0f;
+  int32_t count = 0;
+  int64_t j = A.start[v];
+  if( j >= 0 )
+  {
+    uint32_t face = 0xFFFFFFFFu;
+    float4 fn = make_float4( 0.0f, 0.0f, 0.0f, 0.0f );
+    float t = 0.0f, u = 0.0f;
+    for( ; j < n_corners && A.skey[j] == (uint32_t)v; ++j )
+    {
+      const uint32_t f = A.sval[j] / 3u;
+      if( f != face )                                  // counts advance after the face's three corners (:580-583): one t per face
+      {
+        face = f; fn = A.face_nor[f];
+        t = 1.0f / ( (float)count + 1.0f ); u = 1.0f - t;
+      }
+      x = t * fn.x + u * x; y = t * fn.y + u * y; z = t * fn.z + u * z;        // msh_vec3_lerp, msh_vec_math.h:1032-1036
+      ++count;
+    }
+  }
+  // :586-592.  norm = (float)sqrt( (double)sum ) is positive exactly where the fp32 sum is (the root of the smallest denormal is a
+  // normal float); a NaN fails the compare, an infinite sum passes it and normalises to NaN
+  const float sum = x * x + y * y + z * z;
+  if( sum > 0.0f ) { const float d = 1.0f / sqrtf( sum ); x *= d; y *= d; z *= d; }
+  else { x = 0.0f; y = 1.0f; z = 0.0f; }
+  if( A.loader_pass )                                  // :743-751
+  {
+    const float d = 1.0f / sqrtf( x * x + y * y + z * z );
+    x *= d; y *= d; z *= d;
+    if( x != x || y != y || z != z ) { x = 0.0f; y = 0.0f; z = 0.0f; }
+  }
+  float* o = A.nor + (size_t)v * A.nor_stride;
+  o[0] = x; o[1] = y; o[2] = z;
+  if( A.counts ) A.counts[v] = count;
+}
+
 } // namespace rs
 
 using namespace rs;
 
 namespace {
 
-struct MeshWorkspace { Buf vert, faces, table, out[7]; };
+struct MeshWorkspace
+{
+  Buf vert, faces, table, out[7];
+  Buf n_pos, n_nor, n_counts, face_nor, key, skey, val, sval, start, tmp;      // the vertex normals' (rs_hip_vertex_normals, rs_hip_cloud_create_from_mesh)
+};
 thread_local MeshWorkspace g_mesh_ws;
 
 struct MeshIn
@@ -194,6 +288,74 @@ int mesh_launch( MeshSampleArgs& A, int64_t first, int64_t count, hipStream_t st
   }
   RS_TRY( hipGetLastError(), "resample: launch" );
   return RS_HIP_OK;
+}
+
+// What rs_hip_vertex_normals refuses, before a device is touched.  scan_indices false: the caller's plan looks at every index anyway.
+int normals_refusal( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces, bool scan_indices )
+{
+  char msg[200];
+  if( !pos || !faces ) return fail( RS_HIP_E_ARG, "vertex_normals: pos and faces are required" );
+  if( n_vertices <= 0 || n_vertices > INT32_MAX ) { snprintf( msg, sizeof(msg), "vertex_normals: %lld vertices: between 1 and INT32_MAX", (long long)n_vertices ); return fail( RS_HIP_E_ARG, msg ); }
+  if( n_faces <= 0 ) { snprintf( msg, sizeof(msg), "vertex_normals: %lld faces: the reference leaves its normals unwritten without one", (long long)n_faces ); return fail( RS_HIP_E_ARG, msg ); }
+  if( n_faces > INT32_MAX / 3 ) { snprintf( msg, sizeof(msg), "vertex_normals: %lld faces: 3 n_faces exceeds INT32_MAX", (long long)n_faces ); return fail( RS_HIP_E_ARG, msg ); }
+  if( scan_indices )
+    for( int64_t i = 0; i < 3 * n_faces; ++i )
+      if( faces[i] < 0 || faces[i] >= n_vertices )
+      {
+        snprintf( msg, sizeof(msg), "vertex_normals: face %lld names vertex %d, outside [0, %lld)", (long long)( i / 3 ), faces[i], (long long)n_vertices );
+        return fail( RS_HIP_E_ARG, msg );
+      }
+  return RS_HIP_OK;
+}
+
+// The three launches and the sort, queued on st.  pos / nor / faces (and counts, may be null) are device pointers; every index in
+// faces is inside [0, n_vertices): the callers' refusals have seen to it.
+int normals_device( const float* pos, int32_t pos_stride, float* nor, int32_t nor_stride, int32_t n_vertices, const int32_t* faces,
+                    int32_t n_faces, int32_t loader_pass, int32_t* counts, hipStream_t st )
+{
+  MeshWorkspace& W = g_mesh_ws;
+  const size_t nc = 3 * (size_t)n_faces;
+  int key_bits = 1; while( key_bits < 32 && ( (uint32_t)( n_vertices - 1 ) >> key_bits ) ) ++key_bits;
+  const size_t tmp_bytes = build_sort_temp_bytes( (int)nc, key_bits );
+  RS_TRY( W.face_nor.ensure( (size_t)n_faces * sizeof(float4) ), "vertex_normals: buffers" );
+  for( Buf* b : { &W.key, &W.skey, &W.val, &W.sval } ) RS_TRY( b->ensure( nc * 4 ), "vertex_normals: buffers" );
+  RS_TRY( W.start.ensure( (size_t)n_vertices * 4 ), "vertex_normals: buffers" );
+  RS_TRY( W.tmp.ensure( tmp_bytes ), "vertex_normals: buffers" );
+  NormalArgs A{};
+  A.pos = pos; A.pos_stride = pos_stride; A.nor = nor; A.nor_stride = nor_stride;
+  A.faces = faces; A.n_vertices = n_vertices; A.n_faces = n_faces; A.loader_pass = loader_pass;
+  A.face_nor = W.face_nor.as<float4>(); A.key = W.key.as<uint32_t>(); A.val = W.val.as<uint32_t>();
+  A.skey = W.skey.as<uint32_t>(); A.sval = W.sval.as<uint32_t>(); A.start = W.start.as<int32_t>(); A.counts = counts;
+  {
+    ProfSpan span( "normals_cross" );
+    hipLaunchKernelGGL( k_face_cross, dim3( blocks_for( n_faces, MESH_BLOCK ) ), dim3( MESH_BLOCK ), 0, st, A );
+  }
+  RS_TRY( hipGetLastError(), "vertex_normals: launch" );
+  {
+    ProfSpan span( "normals_group" );
+    if( build_sort_pairs( W.tmp.p, tmp_bytes, A.key, W.skey.as<uint32_t>(), A.val, W.sval.as<uint32_t>(), (int)nc, key_bits, st ) )
+      return fail( RS_HIP_E_RUNTIME, "vertex_normals: device sort failed" );
+    RS_TRY( hipMemsetAsync( W.start.p, 0xFF, (size_t)n_vertices * 4, st ), "vertex_normals: launch" );
+    hipLaunchKernelGGL( k_span_start, dim3( blocks_for( (long long)nc, MESH_BLOCK ) ), dim3( MESH_BLOCK ), 0, st, A );
+  }
+  RS_TRY( hipGetLastError(), "vertex_normals: launch" );
+  {
+    ProfSpan span( "normals_chain" );
+    hipLaunchKernelGGL( k_vertex_chain, dim3( blocks_for( n_vertices, MESH_BLOCK ) ), dim3( MESH_BLOCK ), 0, st, A );
+  }
+  RS_TRY( hipGetLastError(), "vertex_normals: launch" );
+  return RS_HIP_OK;
+}
+
+// the prepared mesh sampled into the level builder's workspace and indexed there
+rs_hip_cloud_t* cloud_from_prepared( MeshSampleArgs& A, hipStream_t st, int64_t count, bool with_nor, float cell_size )
+{
+  // positions and normals go straight into the workspace the index build reads (as rs_hip_cloud_create_level's gather does)
+  float *d_pos = nullptr, *d_nor = nullptr;
+  if( api_level_workspace( (size_t)count, with_nor, &d_pos, &d_nor ) ) return nullptr;
+  A.out_pos = d_pos; A.out_nor = d_nor;
+  if( count > 0 && mesh_launch( A, 0, count, st ) ) return nullptr;
+  return api_cloud_from_level_workspace( with_nor, (int32_t)count, cell_size );
 }
 
 } // namespace
@@ -262,12 +424,46 @@ rs_hip_cloud_t* rs_hip_cloud_create_resampled( const float* pos, const float* no
   MeshSampleArgs A; hipStream_t st = nullptr; int64_t count = 0;
   if( mesh_prepare( M, &count, A, &st ) ) return nullptr;
   if( n_samples ) *n_samples = count;
-  // positions and normals go straight into the workspace the index build reads (as rs_hip_cloud_create_level's gather does)
-  float *d_pos = nullptr, *d_nor = nullptr;
-  if( api_level_workspace( (size_t)count, nor != nullptr, &d_pos, &d_nor ) ) return nullptr;
-  A.out_pos = d_pos; A.out_nor = d_nor;
-  if( count > 0 && mesh_launch( A, 0, count, st ) ) return nullptr;
-  return api_cloud_from_level_workspace( nor != nullptr, (int32_t)count, cell_size );
+  return cloud_from_prepared( A, st, count, nor != nullptr, cell_size );
+}
+
+int rs_hip_vertex_normals( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                           int32_t loader_pass, float* out_nor, int32_t* counts )
+{
+  if( !out_nor ) return fail( RS_HIP_E_ARG, "vertex_normals: out_nor is required" );
+  int rc = normals_refusal( pos, n_vertices, faces, n_faces, true ); if( rc ) return rc;
+  hipStream_t st = nullptr;
+  rc = api_ready( &st ); if( rc ) return rc;
+  MeshWorkspace& W = g_mesh_ws;
+  const size_t nv = (size_t)n_vertices, nf = (size_t)n_faces;
+  RS_TRY( W.n_pos.ensure( nv * 12 ), "vertex_normals: buffers" );
+  RS_TRY( W.n_nor.ensure( nv * 12 ), "vertex_normals: buffers" );
+  RS_TRY( W.faces.ensure( nf * 12 ), "vertex_normals: buffers" );
+  if( counts ) RS_TRY( W.n_counts.ensure( nv * 4 ), "vertex_normals: buffers" );
+  RS_TRY_DRAIN( st, hipMemcpyAsync( W.n_pos.p, pos, nv * 12, hipMemcpyHostToDevice, st ), "vertex_normals: upload" );
+  RS_TRY_DRAIN( st, hipMemcpyAsync( W.faces.p, faces, nf * 12, hipMemcpyHostToDevice, st ), "vertex_normals: upload" );
+  rc = normals_device( W.n_pos.as<float>(), 3, W.n_nor.as<float>(), 3, (int32_t)n_vertices, W.faces.as<int32_t>(), (int32_t)n_faces,
+                       loader_pass ? 1 : 0, counts ? W.n_counts.as<int32_t>() : nullptr, st );
+  if( rc ) { (void)hipStreamSynchronize( st ); return rc; }
+  RS_TRY_DRAIN( st, hipMemcpyAsync( out_nor, W.n_nor.p, nv * 12, hipMemcpyDeviceToHost, st ), "vertex_normals: download" );
+  if( counts ) RS_TRY_DRAIN( st, hipMemcpyAsync( counts, W.n_counts.p, nv * 4, hipMemcpyDeviceToHost, st ), "vertex_normals: download" );
+  RS_TRY( hipStreamSynchronize( st ), "vertex_normals: kernel" );
+  return RS_HIP_OK;
+}
+
+rs_hip_cloud_t* rs_hip_cloud_create_from_mesh( const float* pos, int64_t n_vertices, const int32_t* faces, int64_t n_faces,
+                                               float cell_size, int64_t* n_samples )
+{
+  if( normals_refusal( pos, n_vertices, faces, n_faces, false ) ) return nullptr;
+  const MeshIn M{ pos, nullptr, nullptr, nullptr, nullptr, nullptr, n_vertices, faces, n_faces };
+  MeshSampleArgs A; hipStream_t st = nullptr; int64_t count = 0;
+  if( mesh_prepare( M, &count, A, &st ) ) return nullptr;            // (the plan refuses an index outside the vertices)
+  if( n_samples ) *n_samples = count;
+  // the normals go into the records k_mesh_sample reads: floats 3..5 of a vertex's twelve
+  MeshWorkspace& W = g_mesh_ws;
+  if( normals_device( W.vert.as<float>(), 12, W.vert.as<float>() + 3, 12, (int32_t)n_vertices, W.faces.as<int32_t>(), (int32_t)n_faces,
+                      1, nullptr, st ) ) { (void)hipStreamSynchronize( st ); return nullptr; }
+  return cloud_from_prepared( A, st, count, true, cell_size );
 }
 
 } // extern "C"
