@@ -46,6 +46,10 @@ int         rs_hip_stream_cu_mask( const uint32_t* mask, int32_t n_words );
 void*       rs_hip_get_stream( void );
 /* ABI/version string, e.g. "rescan_hip 0.1 gfx950". */
 const char* rs_hip_version( void );
+/* The value the library would use now for one of its environment switches (RS_HIP_..., the table of rescan_amd/csrc/rs_switches.h:
+ * the environment as read at the time that switch is read, or what its setter stored since).  A flag gives 0 or 1, a word 1 when
+ * set.  RS_HIP_E_ARG for a name that is not in the table.  Needs no device. */
+int         rs_hip_switch_get( const char* name, double* value );
 
 /* Per-kernel timing with HIP events recorded on the launch stream.  While enabled, each
  * launch of a hot kernel is bracketed by an event pair; rs_hip_profile_read() synchronises

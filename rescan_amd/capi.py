@@ -26,6 +26,7 @@ SIGNATURES = {
     "rs_hip_stream_cu_mask": (C.c_int, [C.c_void_p, C.c_int32]),
     "rs_hip_get_stream": (C.c_void_p, []),
     "rs_hip_version": (C.c_char_p, []),
+    "rs_hip_switch_get": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
     "rs_hip_profile_enable": (C.c_int, [C.c_int]),
     "rs_hip_profile_reset": (C.c_int, []),
     "rs_hip_profile_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
@@ -640,49 +641,70 @@ def cloud_build_seconds(reset=False):
     return [float(x) for x in out], int(n)
 
 
-def icp_reference_order_below(n_points=-1):
-    """Sources of at most n_points points run the estimator in the reference's accumulation order (bit-identical
-    results); -1 only reads.  Returns the previous threshold."""
-    return int(load().rs_hip_icp_reference_order_below(int(n_points)))
+def switch_get(name):
+    """The value the library would use now for an environment switch of its table (rescan_amd/csrc/rs_switches.h): a flag gives 0.0 or
+    1.0.  Raises for a name that is not in the table.  Needs no device."""
+    v = C.c_double(0.0)
+    _check(load().rs_hip_switch_get(name.encode(), C.byref(v)))
+    return float(v.value)
 
 
-def icp_replay_below(n_points=-1):
-    """Threshold up to which sources above the reference-order threshold get the reference's sums computed in parallel
-    (same bits); -1 only reads.  Returns the previous threshold."""
-    return int(load().rs_hip_icp_replay_below(int(n_points)))
+# The setters of the switches that have one: (wrapper, its argument and default, result type, what it sets).  Each forwards to
+# rs_hip_<wrapper>: a negative argument only reads, the previous value comes back.
+_SETTERS = [
+    ("icp_reference_order_below", "n_points", -1, int,
+     "Sources of at most n_points points run the estimator in the reference's accumulation order (bit-identical results)."),
+    ("icp_replay_below", "n_points", -1, int,
+     "Threshold up to which sources above the reference-order threshold get the reference's sums computed in parallel (same bits)."),
+    ("icp_lane_chains_below", "n_points", -1, int,
+     "Sources above the two thresholds before and of at most n_points points: the reference's centroid chains by one wave per chain "
+     "+ fp64 moments (any number of problems side by side)."),
+    ("icp_early_plain", "on", -1, int, "Plain (chain-free) early iterations of the lane / grid chain estimators (default on)."),
+    ("icp_plain_from_records", "on", -1, int,
+     "1: plain iterations read the searches' 48-byte records again (default 0: moments from the matches, no records written)."),
+    ("icp_update_fenced", "on", -1, int,
+     "1: the launch that ends an iteration hands its sums over by two full fences again (default 0: agent-scope atomics; the same bits)."),
+    ("icp_stop_guard", "guard", -1.0, float, "Width of the stop test's guard (0: off; default 1.5e-6)."),
+    ("icp_exact_centroids", "on", -1, int,
+     "Sources above both thresholds: centre the fp64 step on the reference's own fp32 centroid chains (default on)."),
+    ("icp_chains_retry_after", "calls", -1, int,
+     "After a source's centroid chains gave up, its next `calls` ICP calls go straight to the replay (default 15; 0: every call tries "
+     "the chains first)."),
+    ("score_scene_space_from", "n_queries", -1, int,
+     "Score batches of at least n_queries (poses x object points) take the scene-space route (queries sorted by scene block)."),
+    ("icp_faith_guess", "permille", -1, int,
+     "Test switch of the sequential estimator's guessed cut (1000: as made, 0: three passes, else scaled)."),
+]
+# ... and the counters next to them: (wrapper, what it counts)
+_COUNTERS = [
+    ("icp_lane_chains_sequential", "(diagnostics) addends the lane chains have added one by one in fp32 since init."),
+    ("icp_stop_guard_redone", "(diagnostics) problems run again in the reference's order because a stop test was decided inside the guard, since init."),
+    ("icp_chains_gave_up", "Calls the grid chains gave up and the replay's pass 2 redid (include/rescan_hip.h)."),
+    ("icp_replay_redone", "Segments the last call's replay walks had to re-add one addend after the other (include/rescan_hip.h)."),
+    ("icp_faith_redone", "Iterations of the sequential estimator whose one-pass statistics + centroids had to be summed again (cumulative)."),
+]
 
 
-def icp_lane_chains_below(n_points=-1):
-    """Sources above the two thresholds before and of at most n_points points: the reference's centroid chains by one wave per chain
-    + fp64 moments (any number of problems side by side); -1 only reads.  Returns the previous threshold."""
-    return int(load().rs_hip_icp_lane_chains_below(int(n_points)))
+def _setter(name, arg, default, kind, doc):
+    def f(value=default):
+        return kind(getattr(load(), "rs_hip_" + name)(kind(value)))
+    f.__name__ = f.__qualname__ = name
+    f.__doc__ = f"{doc}  {arg} < 0 only reads.  Returns the previous value."
+    return f
 
 
-def icp_lane_chains_sequential():
-    """(diagnostics) addends the lane chains have added one by one in fp32 since init."""
-    return int(load().rs_hip_icp_lane_chains_sequential())
+def _counter(name, doc):
+    def f():
+        return int(getattr(load(), "rs_hip_" + name)())
+    f.__name__ = f.__qualname__ = name
+    f.__doc__ = doc
+    return f
 
 
-def icp_stop_guard_redone():
-    """(diagnostics) problems run again in the reference's order because a stop test was decided inside the guard, since init."""
-    return int(load().rs_hip_icp_stop_guard_redone())
-
-
-def icp_early_plain(on=-1):
-    """Plain (chain-free) early iterations of the lane / grid chain estimators (default on); -1 only reads.  Returns the previous setting."""
-    return int(load().rs_hip_icp_early_plain(int(on)))
-
-
-def icp_plain_from_records(on=-1):
-    """1: plain iterations read the searches' 48-byte records again (default 0: moments from the matches, no records written); -1 only reads.
-    Returns the previous setting."""
-    return int(load().rs_hip_icp_plain_from_records(int(on)))
-
-
-def icp_update_fenced(on=-1):
-    """1: the launch that ends an iteration hands its sums over by two full fences again (default 0: agent-scope atomics; the same bits);
-    -1 only reads.  Returns the previous setting."""
-    return int(load().rs_hip_icp_update_fenced(int(on)))
+for _row in _SETTERS:
+    globals()[_row[0]] = _setter(*_row)
+for _row in _COUNTERS:
+    globals()[_row[0]] = _counter(*_row)
 
 
 def icp_state_layout():
@@ -690,48 +712,6 @@ def icp_state_layout():
     a, b = C.c_int32(0), C.c_int32(0)
     load().rs_hip_icp_state_layout(C.byref(a), C.byref(b))
     return int(a.value), int(b.value)
-
-
-def icp_stop_guard(guard=-1.0):
-    """Width of the stop test's guard (0: off; default 1.5e-6); < 0 only reads.  Returns the previous width."""
-    return float(load().rs_hip_icp_stop_guard(float(guard)))
-
-
-def icp_exact_centroids(on=-1):
-    """Sources above both thresholds: centre the fp64 step on the reference's own fp32 centroid chains (default on); -1 only
-    reads.  Returns the previous setting."""
-    return int(load().rs_hip_icp_exact_centroids(int(on)))
-
-
-def icp_chains_retry_after(calls=-1):
-    """After a source's centroid chains gave up, its next `calls` ICP calls go straight to the replay (default 15; 0: every call tries
-    the chains first); -1 only reads.  Returns the previous value."""
-    return int(load().rs_hip_icp_chains_retry_after(int(calls)))
-
-
-def score_scene_space_from(n_queries=-1):
-    """Score batches of at least n_queries (poses x object points) take the scene-space route (queries sorted by scene block);
-    -1 only reads.  Returns the previous threshold."""
-    return int(load().rs_hip_score_scene_space_from(int(n_queries)))
-
-
-def icp_chains_gave_up():
-    """Calls the grid chains gave up and the replay's pass 2 redid (include/rescan_hip.h)."""
-    return int(load().rs_hip_icp_chains_gave_up())
-
-
-def icp_replay_redone():
-    return int(load().rs_hip_icp_replay_redone())
-
-
-def icp_faith_guess(permille=-1):
-    """Test switch of the sequential estimator's guessed cut (1000: as made, 0: three passes, else scaled); returns the previous value."""
-    return int(load().rs_hip_icp_faith_guess(int(permille)))
-
-
-def icp_faith_redone():
-    """Iterations of the sequential estimator whose one-pass statistics + centroids had to be summed again (cumulative)."""
-    return int(load().rs_hip_icp_faith_redone())
 
 
 def icp_align(source, target, T1, T2=IDENTITY, max_dist=0.1, max_angle=np.deg2rad(60.0), max_iter=100,

@@ -10,6 +10,7 @@
 #include "rs_device.h"
 #include "rs_host.h"
 #include "rs_math.h"
+#include "rs_switches.h"
 #include "rs_voxel.h"
 
 #include <algorithm>
@@ -184,11 +185,11 @@ std::mutex g_faith_redone_mu;
 bool g_prof = false;
 // The estimator of icp_estimate_rigid_xform_pt2pl (lib/rs/icp.h:210-298) by source size — round 6: the policy priced against the bar on every
 // reference fixture (profiles/r06/estimator_policy.txt):
-//   n <= g_ref_order_below (16 384)  the reference's own accumulation order and precisions (k_icp_faithful): its bits.  Every level-2 object of the
+//   n <= REF_ORDER_BELOW (16 384)    the reference's own accumulation order and precisions (k_icp_faithful): its bits.  Every level-2 object of the
 //                                    reference's call sites (2-10 k points); up to ~10 k points the sequential chains cost no more than the launches of
 //                                    anything parallel (60-90 us per iteration either way), at 16 k 150 against 75.
-//   n <= g_replay_below (0: off)     the same bits computed in parallel ("replay"): opt-in.
-//   n <= g_lane_below (65 536)       LANE chains: the reference's 2.5 sigma cut and its seven centroid sums bit for bit by one wave per chain +
+//   n <= REPLAY_BELOW (0: off)       the same bits computed in parallel ("replay"): opt-in.
+//   n <= LANE_CHAINS_BELOW (65 536)  LANE chains: the reference's 2.5 sigma cut and its seven centroid sums bit for bit by one wave per chain +
 //                                    fp64 moments; any number of differently sized problems per launch (rs_hip_icp_align_multi) — every icp_align
 //                                    call site of the reference (level-2 objects 2-10 k points, scene extracts up to ~50 k: SURVEY §8 a6).
 //                                    <= 3e-6 from the reference's pose on its fixtures, equal iteration counts; 110 instead of 520 us per iteration at 50 k.
@@ -197,17 +198,12 @@ bool g_prof = false;
 //                                    the sums by pass 2 of the replay.
 // RS_HIP_EXACT_CENTROIDS=0: plain fp64 moments for everything above the first two thresholds (up to 2e-4 from the reference: NOT within the bar's
 // margin — kept for measurements).  rs_hip_icp_reference_order_below( 65536 ) brings the reference's bits back for every call site.
-// After a source's centroid chains gave a problem up, its next `g_chains_retry_after` calls go straight to the replay (rs_hip_icp_chains_retry_after).
-std::atomic<int> g_chains_retry_after{ getenv( "RS_HIP_CHAINS_RETRY_AFTER" ) ? atoi( getenv( "RS_HIP_CHAINS_RETRY_AFTER" ) ) : 15 };
-std::atomic<int> g_ref_order_below{ getenv( "RS_HIP_REF_ORDER_BELOW" ) ? atoi( getenv( "RS_HIP_REF_ORDER_BELOW" ) ) : 16384 };
+// After a source's centroid chains gave a problem up, its next CHAINS_RETRY_AFTER calls go straight to the replay (rs_hip_icp_chains_retry_after).
+// (The thresholds are rows of rs_switches.h: read when the library is loaded, changed by their setters.)
 std::atomic<int> g_chains_gave_up{ 0 };
-std::atomic<int> g_faith_guess_permille{ getenv( "RS_HIP_FAITH_GUESS" ) ? atoi( getenv( "RS_HIP_FAITH_GUESS" ) ) : 1000 };
-std::atomic<int> g_exact_centroids{ getenv( "RS_HIP_EXACT_CENTROIDS" ) ? atoi( getenv( "RS_HIP_EXACT_CENTROIDS" ) ) : 1 };
-std::atomic<int> g_replay_below{ getenv( "RS_HIP_REPLAY_BELOW" ) ? atoi( getenv( "RS_HIP_REPLAY_BELOW" ) ) : 0 };
-std::atomic<int> g_lane_below{ getenv( "RS_HIP_LANE_CHAINS_BELOW" ) ? atoi( getenv( "RS_HIP_LANE_CHAINS_BELOW" ) ) : 65536 };
 // ... of a call with ONE problem, whose grid chains have the chip to themselves: the same sums — the same poses, bit for bit — faster from
 // ~28 k points on (tools/lane_vs_grid.py, us per iteration lane | grid: 17 k 74 | 80, 25 k 80 | 80, 30 k 84 | 80, 40 k 101 | 90, 50 k 111 | 91,
-// 65 k 130 | 97); batches keep the lane chains up to g_lane_below (a walk per problem side by side: eight 50 k-point refines 20 us per
+// 65 k 130 | 97); batches keep the lane chains up to LANE_CHAINS_BELOW (a walk per problem side by side: eight 50 k-point refines 20 us per
 // problem and iteration).  A threshold set beyond 65 536 (rs_hip_icp_lane_chains_below) means "the lane chains, whatever the call" and
 // holds for single calls too; any other setting caps them at 28 672.
 // The two source sizes the policy is keyed on: object-sized sources (the sequential reference order of a bit-exact run, the lane chains'
@@ -231,10 +227,10 @@ struct IcpChoice { IcpEstimator est; bool guard; };
 // applies: only where the estimator is not the reference's order AND a bit-exact one exists to run the problem again with.
 IcpChoice icp_choose( int n_source, int n_problems, int centroid_mode, bool force_bits )
 {
-  if( n_source <= ( force_bits ? ICP_OBJECT_PTS : g_ref_order_below.load() ) ) return { ICP_EST_REF_ORDER, false };
-  if( n_source <= ( force_bits ? ICP_EXACT_PTS : g_replay_below.load() ) ) return { ICP_EST_REPLAY, false };
+  if( n_source <= ( force_bits ? ICP_OBJECT_PTS : sw_int( SW_REF_ORDER_BELOW ) ) ) return { ICP_EST_REF_ORDER, false };
+  if( n_source <= ( force_bits ? ICP_EXACT_PTS : sw_int( SW_REPLAY_BELOW ) ) ) return { ICP_EST_REPLAY, false };
   if( centroid_mode == 0 ) return { ICP_EST_MOMENTS, false };
-  const int below = g_lane_below.load();
+  const int below = sw_int( SW_LANE_CHAINS_BELOW );
   const IcpEstimator est = n_source <= ( n_problems > 1 ? below : lane_single_cap( below ) ) ? ICP_EST_LANE_CHAINS
                          : centroid_mode == 1 ? ICP_EST_GRID_CHAINS : ICP_EST_RECORDS;
   return { est, n_source <= ICP_EXACT_PTS };
@@ -242,11 +238,10 @@ IcpChoice icp_choose( int n_source, int n_problems, int centroid_mode, bool forc
 // The stop test's guard (round 6).  icp_align stops when |err - prev_err| < 1e-5 (icp.h:489).  The lane / grid chains follow the
 // reference's errors to 1e-8 ... 6e-7 (their moments are exact where the reference rounds): when a decisive difference passes within
 // that of 1e-5 the decision can fall the other way — one iteration more or less, 1e-4 ... 2e-4 in the pose; measured: 2 of 49
-// object-sized runs, profiles/r06/stop_test_guard.txt.  A problem whose |delta err| comes within g_stop_guard of the threshold in any
+// object-sized runs, profiles/r06/stop_test_guard.txt.  A problem whose |delta err| comes within STOP_GUARD of the threshold in any
 // iteration that can stop (i > 5) is therefore RUN AGAIN in the reference's own order (sequential chains up to 65 536 points, their
 // parallel form up to 262 144): the reference's bits.  ~20 % of stop-test calls at 1.5e-6; larger sources have no bit-exact estimator
 // to fall back on (0.5 ms per iteration at 1 M points were never the default) and keep their result.  RS_HIP_STOP_GUARD=0: off.
-std::atomic<float> g_stop_guard{ getenv( "RS_HIP_STOP_GUARD" ) ? (float)atof( getenv( "RS_HIP_STOP_GUARD" ) ) : 1.5e-6f };
 std::atomic<long long> g_stop_guard_redone{ 0 };      // (diagnostics: rs_hip_icp_stop_guard_redone)
 // PLAIN early iterations (round 6).  The reference's centroid chains decide where the iteration CONVERGES; an iteration far from the end only has
 // to bring the pose near, and ICP forgets how it got there at its own contraction rate (measured on the headline, the chains in the last m
@@ -256,13 +251,12 @@ std::atomic<long long> g_stop_guard_redone{ 0 };      // (diagnostics: rs_hip_ic
 // iterations before its end (m = 2 and m = 3 are the same few 1e-6 from the reference's pose on six rooms — <= 3.7e-6 / <= 2.6e-6, neither
 // monotone in m — m = 1 is not: 1.1e-5, outside the 1e-5 this policy is held to); three in a call with the stop test (first decision at
 // i = 6, icp.h:489), which runs plain in its first four iterations, and only where no bit-exact estimator guards the decision anyway
-// (sources above 262 144 points: g_stop_guard).  A ten-iteration call at 1 M points: 2.52 -> 2.14 ms.  RS_HIP_EARLY_PLAIN=0: off;
+// (sources above 262 144 points: STOP_GUARD).  A ten-iteration call at 1 M points: 2.52 -> 2.14 ms.  RS_HIP_EARLY_PLAIN=0: off;
 // rs_hip_icp_early_plain().  RS_HIP_EARLY_TAIL=m: m chain iterations kept in both kinds of call (tools/early_plain_table.py).
-std::atomic<int> g_early_plain{ getenv( "RS_HIP_EARLY_PLAIN" ) ? atoi( getenv( "RS_HIP_EARLY_PLAIN" ) ) : 1 };
 inline int icp_plain_iterations( int n_source, int max_iter, bool fixed_iters )
 {
-  if( !g_early_plain.load() ) return 0;
-  static const int forced = getenv( "RS_HIP_EARLY_TAIL" ) ? atoi( getenv( "RS_HIP_EARLY_TAIL" ) ) : 0;
+  if( !sw_int( SW_EARLY_PLAIN ) ) return 0;
+  const int forced = sw_int( SW_EARLY_TAIL );
   const int keep = forced > 0 ? forced : ( fixed_iters ? 2 : 3 );      // chain iterations before a result can be returned
   const int tail = std::max( 0, max_iter - keep );
   // (by SIZE, not by which kernels run the chains: an object refine contracts too slowly for this — rs_hip_icp_lane_chains_below( 0 ) puts
@@ -277,7 +271,6 @@ inline int icp_plain_iterations( int n_source, int max_iter, bool fixed_iters )
 // L.rec == null and k_plain_moments forms the moments from m_slot / m_d2 / m_dot in tile order (rs_icp_estimate.hip); the iterations that
 // keep the chains, or the RECORDS estimator's own, get their records from their own search as before.  RS_HIP_PLAIN_RECORDS=1 /
 // rs_hip_icp_plain_from_records( 1 ): the plain step from records again (A/B runs, tests).
-std::atomic<int> g_plain_records{ getenv( "RS_HIP_PLAIN_RECORDS" ) ? atoi( getenv( "RS_HIP_PLAIN_RECORDS" ) ) : 0 };
 std::mutex g_prof_mutex;
 struct ProfEntry { std::vector<std::pair<hipEvent_t, hipEvent_t>> spans; int64_t launches = 0; double ms = 0.0; };
 std::map<std::string, ProfEntry> g_profmap;
@@ -322,7 +315,7 @@ struct ProfChain
   bool on = true;
   ProfChain()
   {
-    static const unsigned every = getenv( "RS_HIP_PROF_EVERY" ) ? (unsigned)std::max( 1, atoi( getenv( "RS_HIP_PROF_EVERY" ) ) ) : 1u;
+    const unsigned every = (unsigned)sw_int( SW_PROF_EVERY );
     thread_local unsigned tick = 0;
     if( g_prof ) on = ( tick++ % every ) == 0;
   }
@@ -399,8 +392,7 @@ float query_extent_limit( int32_t n, size_t occupied_cells, float cell )
   // ... and never more than 0.3 m: a sparse cloud (a subsampled level, a random subset) searched in a denser one would
   // otherwise get tiles whose box is mostly the empty space between its points (1000 points against a 200 k scan:
   // 404 -> 60 us per ICP iteration with the cap)
-  static const float cap = getenv( "RS_HIP_TILE_EXTENT_MAX" ) ? (float)atof( getenv( "RS_HIP_TILE_EXTENT_MAX" ) ) : 0.3f;
-  return std::min( cap, std::max( 0.25f, 12.0f * spacing ) );
+  return std::min( sw_float( SW_TILE_EXTENT_MAX ), std::max( 0.25f, 12.0f * spacing ) );
 }
 
 } // namespace
@@ -426,7 +418,7 @@ int rs_hip_init( int device )
   // does bench.py).  Opt-in: a library does not change a process's scheduling policy by itself (8 ranks x 3 busy-waiting threads on
   // a host with a CPU quota would starve each other).  Refused (harmlessly) when the process has set the device up already.
   {
-    const char* sch = getenv( "RS_HIP_SCHEDULE" );
+    const char* sch = sw_word( SW_SCHEDULE );
     if( sch && !std::strcmp( sch, "spin" ) ) (void)hipSetDeviceFlags( hipDeviceScheduleSpin );
     (void)hipGetLastError();
   }
@@ -639,8 +631,7 @@ static rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, in
         }
         if( per_cell >= 4.0f || attempt == 7 ) { cell_size = 2.0f * c0 / std::sqrt( std::max( per_cell, 1.0f ) ); break; }
       }
-      static const float scale = getenv( "RS_HIP_AUTO_CELL_SCALE" ) ? (float)atof( getenv( "RS_HIP_AUTO_CELL_SCALE" ) ) : 1.0f;
-      cell_size = std::min( std::max( cell_size * scale, 0.005f ), 2.0f );
+      cell_size = std::min( std::max( cell_size * sw_float( SW_AUTO_CELL_SCALE ), 0.005f ), 2.0f );
     }
   }
   int dims[3] = { 1, 1, 1 };
@@ -853,8 +844,7 @@ namespace {
 // everything in phase A — there the stragglers hide behind other tiles and the hand-off measured slower.
 inline int handoff_threshold( long long total_tiles )
 {
-  static const int forced = getenv( "RS_HIP_SOLO_STAGES" ) ? atoi( getenv( "RS_HIP_SOLO_STAGES" ) ) : -1;
-  static const int forced_k = getenv( "RS_HIP_HANDOFF_K" ) ? atoi( getenv( "RS_HIP_HANDOFF_K" ) ) : -1;
+  const int forced = sw_int( SW_SOLO_STAGES ), forced_k = sw_int( SW_HANDOFF_K );
   if( forced > 0 ) return forced | ( std::max( 0, forced_k ) << 16 );
   if( total_tiles > 24000 ) return 0x7fffffff;
   const int k_always = forced_k >= 0 ? forced_k : 1;
@@ -927,19 +917,15 @@ int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tg
     return rc;
   L.queue = g_ws.queue.as<int>(); L.queue_count = g_ws.queue_count.as<int>();
   L.solo_stages = handoff_threshold( (long long)cx.total_tiles );
-  static const int heavy_streamed = getenv( "RS_HIP_HEAVY_STREAMED" ) ? atoi( getenv( "RS_HIP_HEAVY_STREAMED" ) ) : 400;
-  static const int heavy_handoff = getenv( "RS_HIP_HEAVY_HANDOFF" ) ? atoi( getenv( "RS_HIP_HEAVY_HANDOFF" ) ) : 600;
-  L.heavy_streamed = heavy_streamed; L.heavy_handoff = heavy_handoff;
-  static const int heavy_total = getenv( "RS_HIP_HEAVY_TOTAL" ) ? atoi( getenv( "RS_HIP_HEAVY_TOTAL" ) ) : 400;
-  L.heavy_total = heavy_total;
+  L.heavy_streamed = sw_int( SW_HEAVY_STREAMED ); L.heavy_handoff = sw_int( SW_HEAVY_HANDOFF ); L.heavy_total = sw_int( SW_HEAVY_TOTAL );
   float* w = g_ws.state.as<float>();
   L.T1 = w + np * ICP_ST_T1; L.active = (int*)( w + np * ICP_ST_ACTIVE ); L.T1_prev = w + np * ICP_ST_T1_PREV;
   L.iters = (int*)( w + np * ICP_ST_ITERS ); L.err = w + np * ICP_ST_ERR; L.prev_err = w + np * ICP_ST_PREV_ERR;
   L.queued = (int*)( w + np * ICP_ST_QUEUED ); L.ticket = (int*)( w + np * ICP_ST_TICKET );
   L.solve = 0; L.iter_index = 0; L.fixed_iters = 0;
-  L.seed = getenv( "RS_HIP_NO_SEED" ) ? 0 : 1;
-  L.by_rows = getenv( "RS_HIP_NO_BY_ROWS" ) ? 0 : 1;
-  L.bounded_only = getenv( "RS_HIP_NO_BOUNDED_ONLY" ) ? 0 : 1;
+  L.seed = sw_flag( SW_NO_SEED ) ? 0 : 1;
+  L.by_rows = sw_flag( SW_NO_BY_ROWS ) ? 0 : 1;
+  L.bounded_only = sw_flag( SW_NO_BOUNDED_ONLY ) ? 0 : 1;
   L.cert_r = nullptr; L.cert_dot = nullptr; L.cert_slack = nullptr; L.tgt_nor_max = tgt->nor_max;
   L.m_slot = g_ws.slot.as<int>(); L.m_d2 = g_ws.d2.as<float>(); L.m_dot = g_ws.dot.as<float>();
   L.stat_acc = nullptr;       // set by the align loop (fp64 estimator only)
@@ -956,7 +942,7 @@ int icp_prepare( IcpCtx& cx, const rs_hip_cloud_t* src, const rs_hip_cloud_t* tg
     }
   }
   L.faith_redone = g_faith_redone.as<int>();
-  L.faith_guess_scale = (float)g_faith_guess_permille.load() / 1000.0f;
+  L.faith_guess_scale = (float)sw_int( SW_FAITH_GUESS ) / 1000.0f;
   g_fills.n = 0; g_fills.state_words = 0;      // (fills an earlier call queued and never launched — it failed before its first kernel — are not this call's)
   if( int rcf = icp_fill( g_ws.queue_count.p, 0, np * 4 ) ) return rcf;
   return RS_HIP_OK;
@@ -1018,11 +1004,11 @@ int icp_enable_certificates( IcpCtx& cx )
 {
   int rc;
   const size_t words = cx.total_pts;
-  if( getenv( "RS_HIP_NO_CERT" ) || !std::isfinite( cx.L.tgt_nor_max ) ) return RS_HIP_OK;
+  if( sw_flag( SW_NO_CERT ) || !std::isfinite( cx.L.tgt_nor_max ) ) return RS_HIP_OK;
   if( ( rc = g_ws.cert_r.ensure( words * 4 ) ) || ( rc = g_ws.cert_dot.ensure( words * 4 ) ) ) return rc;
   if( int rcf = icp_fill( g_ws.cert_r.p, 0xFF, words * 4 ) ) return rcf;      // NaN: no certificate
   cx.L.cert_r = g_ws.cert_r.as<float>(); cx.L.cert_dot = g_ws.cert_dot.as<float>();
-  if( !getenv( "RS_HIP_NO_RANK_CERT" ) )            // read only next to a valid cert_r, written with every fresh one: no initialisation
+  if( !sw_flag( SW_NO_RANK_CERT ) )            // read only next to a valid cert_r, written with every fresh one: no initialisation
   {
     if( ( rc = g_ws.cert_slack.ensure( words * 4 ) ) ) return rc;
     cx.L.cert_slack = g_ws.cert_slack.as<float>();
@@ -1031,15 +1017,15 @@ int icp_enable_certificates( IcpCtx& cx )
 }
 
 // ---- diagnostics (RS_HIP_DEBUG / RS_HIP_DEBUG_CYCLES): one iteration per chunk, device timers per tile ----
-void icp_debug_before( IcpCtx& cx, int n )
+void icp_debug_before( IcpCtx& cx, int n, bool cycles )
 {
   static DevBuf dbgbuf;
 #ifndef RS_DBG
 #define RS_DBG 0
 #endif
-  if( getenv( "RS_HIP_DEBUG_CYCLES" ) && !RS_DBG )
+  if( cycles && !RS_DBG )
   { static bool told = false; if( !told ) fprintf( stderr, "[rs_hip] RS_HIP_DEBUG_CYCLES needs the diagnostic build: tools/variant.sh dbg -DRS_DBG=1, then RS_HIP_LIB=.../librescan_hip_dbg.so\n" ); told = true; }
-  if( RS_DBG && getenv( "RS_HIP_DEBUG_CYCLES" ) && n == 1 )
+  if( RS_DBG && cycles && n == 1 )
   {
     if( dbgbuf.ensure( (size_t)cx.n_waves * 48 + 64 ) ) return;
     (void)hipMemsetAsync( (char*)dbgbuf.p + (size_t)cx.n_waves * 48, 0, 64, g_stream );
@@ -1142,7 +1128,7 @@ int icp_lane_prepare( IcpCtx& cx, ChainBufs& CB )
       ( rc = g_ws.mom_part.ensure( np * (size_t)cx.L.n_mom_blocks * ICP_NMOM * 8 ) ) ||
       ( rc = g_ws.ch_segsum.ensure( 8 * ( rows + 4 * np ) * 4 ) ) ) return rc;
   CB.addends = g_ws.ch_segsum.as<float>();      // (the grid chains' buffer: the two estimators never run in one call)
-  if( getenv( "RS_HIP_LANE_DEBUG" ) )
+  if( sw_flag( SW_LANE_DEBUG ) )
   {
     if( ( rc = g_ws.ch_dbg.ensure( np * CH_ROWS * 16 ) ) ) return rc;
     HIP_TRY( hipMemsetAsync( g_ws.ch_dbg.p, 0, np * CH_ROWS * 16, g_stream ), RS_HIP_E_RUNTIME );
@@ -1221,13 +1207,13 @@ int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
     if( ( rc = g_ws.ch_done.ensure( np * 8 ) ) ) return rc;
     if( int rcf = icp_fill( g_ws.ch_done.p, 0, np * 8 ) ) return rcf;
     CB.done = g_ws.ch_done.as<int>(); CB.failed = (int*)( g_ws.state.as<float>() + np * ICP_ST_FAILED );      // (zero since icp_upload_state)
-    if( getenv( "RS_HIP_CHAIN_DEBUG" ) )
+    if( const int dbg_reps = sw_int( SW_CHAIN_DEBUG ) )      // (at least 1 when the name is set)
     {
       if( ( rc = g_ws.ch_dbg.ensure( rows * ( 4 + 64 * 8 ) * 4 ) ) ) return rc;
-      CB.dbg = g_ws.ch_dbg.as<int>(); CB.dbg_reps = std::max( 1, atoi( getenv( "RS_HIP_CHAIN_DEBUG" ) ) );
+      CB.dbg = g_ws.ch_dbg.as<int>(); CB.dbg_reps = dbg_reps;
       // the walk writes its mismatch marker only where it finds 0: a fresh (or an earlier call's) buffer must not speak for this one
       HIP_TRY( hipMemsetAsync( g_ws.ch_dbg.p, 0, rows * ( 4 + 64 * 8 ) * 4, g_stream ), RS_HIP_E_RUNTIME );
-      if( !getenv( "RS_HIP_CHAIN_DEBUG_NO_SELFCHECK" ) )      // (the self-check redoes every step the slow way: without it the stamps are the walk's real times)
+      if( !sw_flag( SW_CHAIN_DEBUG_NO_SELFCHECK ) )      // (the self-check redoes every step the slow way: without it the stamps are the walk's real times)
       {
         if( ( rc = g_ws.ch_chk.ensure( rows * ( 4 + 3 * 4096 ) * 4 ) ) ) return rc;
         HIP_TRY( hipMemsetAsync( g_ws.ch_chk.p, 0, rows * ( 4 + 3 * 4096 ) * 4, g_stream ), RS_HIP_E_RUNTIME );
@@ -1266,7 +1252,7 @@ int icp_estimator_prepare( IcpCtx& cx, IcpEst& E )
 // Enqueues the estimator launches of iteration i; returns the RS_HIP_ICP_STEP_* kind of what it launched.
 int icp_step( IcpCtx& cx, IcpEst& E, int i )
 {
-  static const int chain_refresh = std::max( 0, getenv( "RS_HIP_CHAIN_REFRESH" ) ? atoi( getenv( "RS_HIP_CHAIN_REFRESH" ) ) : 0 );
+  const int chain_refresh = sw_int( SW_CHAIN_REFRESH );
   switch( E.est )
   {
   case ICP_EST_REF_ORDER:   launch_icp_faithful( cx.L, g_stream ); break;
@@ -1302,7 +1288,7 @@ int icp_step( IcpCtx& cx, IcpEst& E, int i )
 // did not fit, then — unless the chains gave the call up — the walks' self-check.
 void icp_debug_report( const IcpEst& E, int n, int centroid_mode, bool gave_up )
 {
-  if( icp_exact_centroids( E.est ) && getenv( "RS_HIP_DEBUG_TOTALS" ) )
+  if( icp_exact_centroids( E.est ) && sw_flag( SW_DEBUG_TOTALS ) )
   {
     std::vector<double> t( (size_t)n * 3 * ICP_NMOM );
     (void)hipMemcpy( t.data(), E.RB.totals, t.size() * 8, hipMemcpyDeviceToHost );
@@ -1383,12 +1369,12 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
   if( srcs && choice.est != ICP_EST_REF_ORDER && choice.est != ICP_EST_LANE_CHAINS ) { set_err( "icp_align_multi: the estimator thresholds changed during the call" ); return RS_HIP_E_ARG; }
   IcpEst E{ choice.est };
   if( ( rc = icp_estimator_prepare( cx, E ) ) ) return rc;
-  // (see g_early_plain.  Scan-sized sources only: the eight 50 k-point refines of bench.py --scaling strong end 2.2e-6 from the reference with the
+  // (see icp_plain_iterations.  Scan-sized sources only: the eight 50 k-point refines of bench.py --scaling strong end 2.2e-6 from the reference with the
   //  chains throughout, 8.7e-6 with three plain iterations, 2.0e-5 with seven or eight — an object refine contracts more slowly than a scan-to-scan fit)
   if( E.est == ICP_EST_GRID_CHAINS || E.est == ICP_EST_RECORDS ) E.n_plain = icp_plain_iterations( cx.L.max_n, max_iter, fixed_iters != 0 );
-  cx.L.stop_guard = ( choice.guard && !fixed_iters && edge ) ? g_stop_guard.load() : 0.0f;
+  cx.L.stop_guard = ( choice.guard && !fixed_iters && edge ) ? sw_float( SW_STOP_GUARD ) : 0.0f;
   const size_t heavy_words = cx.heavy_words;
-  const bool reorder = !getenv( "RS_HIP_NO_LPT" );
+  const bool reorder = !sw_flag( SW_NO_LPT ), warm = !sw_flag( SW_NO_WARM );
   if( reorder )
   {
     if( ( rc = g_ws.order_a.ensure( heavy_words * 4 ) ) || ( rc = g_ws.order_b.ensure( heavy_words * 4 ) ) ) return rc;
@@ -1400,18 +1386,18 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
   // tests), so iterations are enqueued back to back and the host looks at the state only once per
   // chunk; problems that stopped inside a chunk turn the rest of its launches into no-ops
   // (every kernel returns at once for an inactive problem).
-  const bool debug = !srcs && ( getenv( "RS_HIP_DEBUG" ) || getenv( "RS_HIP_DEBUG_CYCLES" ) );
-  static const int chunk_env = getenv( "RS_HIP_ICP_CHUNK" ) ? atoi( getenv( "RS_HIP_ICP_CHUNK" ) ) : 4;
+  const bool debug_cycles = sw_flag( SW_DEBUG_CYCLES ), debug = !srcs && ( sw_flag( SW_DEBUG ) || debug_cycles );
+  const int chunk_env = sw_int( SW_ICP_CHUNK );
   const size_t np = (size_t)n, state_bytes = np * ICP_STATE_WORDS * 4;
   float* hS = g_ws.h_b.as<float>();
   const int* hActive = (const int*)( hS + np * ICP_ST_ACTIVE );
   const long long total_tiles = (long long)cx.total_tiles;
-  static const long long coop_all_below = getenv( "RS_HIP_COOP_ALL_BELOW" ) ? atoll( getenv( "RS_HIP_COOP_ALL_BELOW" ) ) : 4096;
-  static const int coop_waves_forced = getenv( "RS_HIP_COOP_WAVES" ) ? atoi( getenv( "RS_HIP_COOP_WAVES" ) ) : 0;
+  const long long coop_all_below = sw_i64( SW_COOP_ALL_BELOW );
+  const int coop_waves_forced = sw_int( SW_COOP_WAVES );
   cx.L.solve = 1; cx.L.fixed_iters = fixed_iters ? 1 : 0;
   // (per ITERATION, not per chunk or call: a traced call runs one iteration per chunk, and the RECORDS estimator's own iterations follow plain ones)
   float4* const rec_all = cx.L.rec;
-  const bool plain_matches = !g_plain_records.load() && ( E.est == ICP_EST_GRID_CHAINS || E.est == ICP_EST_RECORDS );
+  const bool plain_matches = !sw_int( SW_PLAIN_RECORDS ) && ( E.est == ICP_EST_GRID_CHAINS || E.est == ICP_EST_RECORDS );
   if( ( rc = icp_fills_flush() ) ) return rc;      // everything the call's first kernels expect zeroed, in one launch
   ProfChain prof;
   int kind = RS_HIP_ICP_STEP_NONE;                  // (rs_hip_icp_trace_begin: the estimator of the iteration just enqueued)
@@ -1425,7 +1411,7 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
     {
       icp_set_radius( cx, max_dist, tmin );
       cx.L.iter_index = i;
-      cx.L.warm = ( i > 0 && !getenv( "RS_HIP_NO_WARM" ) ) ? 1 : 0;   // every active problem wrote m_slot in iteration i-1
+      cx.L.warm = ( i > 0 && warm ) ? 1 : 0;   // every active problem wrote m_slot in iteration i-1
       // launches of a few thousand tiles go straight to the cooperative kernel (launch_icp_corr); it is bound by its
       // heaviest tile while the list is short (8 waves per tile), by throughput beyond (4)
       cx.L.coop_all = total_tiles <= coop_all_below ? 1 : 0;
@@ -1437,7 +1423,7 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
         cx.L.heavy_out = ( i & 1 ) ? g_ws.order_b.as<int>() : g_ws.order_a.as<int>();
       }
       cx.L.rec = ( plain_matches && i < E.n_plain ) ? nullptr : rec_all;      // a plain iteration's search leaves slot, dist² and dot only
-      if( debug ) icp_debug_before( cx, n );
+      if( debug ) icp_debug_before( cx, n, debug_cycles );
       prof.mark( "nn_icp" ); launch_icp_corr( cx.L, g_stream );
       if( debug ) icp_debug_after( cx, cx.L.max_n, n, i, max_dist );
       prof.mark( "icp_moments" ); kind = icp_step( cx, E, i );
@@ -1506,8 +1492,8 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
   // (default 4 GB) — the problems are independent, so the results are those of the one batch.
   // (the arguments first: nothing below may read through them before they are known to be there)
   if( !source || !target || !T1s || !T2 || !errs || n < 0 ) { set_err( "icp_align_batch: bad arguments" ); return RS_HIP_E_ARG; }
-  static const double cap = getenv( "RS_HIP_ICP_BATCH_BYTES" ) ? atof( getenv( "RS_HIP_ICP_BATCH_BYTES" ) ) : 4e9;
-  const bool per_point_records = source && source->n > g_ref_order_below.load();
+  const double cap = sw_double( SW_ICP_BATCH_BYTES );
+  const bool per_point_records = source && source->n > sw_int( SW_REF_ORDER_BELOW );
   // (96 B per point: the 48-byte records + what a slice that falls back to the replay adds — its segment rows, ~35 / 128 x ( 8 + 24 + sizeof( ReplaySeg ) ) ≈ 48 B per point)
   const int slice = per_point_records ? std::max( 1, (int)std::min<double>( (double)std::max( n, 1 ), cap / ( 96.0 * (double)std::max( source->n, 1 ) ) ) ) : std::max( n, 1 );
   for( int p0 = 0; p0 < std::max( n, 1 ); p0 += slice )
@@ -1516,15 +1502,15 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
     float* T = T1s ? T1s + 16 * (size_t)p0 : nullptr; float* e = errs ? errs + p0 : nullptr; int32_t* it = iters ? iters + p0 : nullptr;
     // (a source whose chains gave up lately: the attempt — a cold search, the iterations up to the give-up, the launches that idle
     //  through the rest of the call: ~1.4 ms at a million points — is skipped; every 16th such call tries the chains again)
-    int mode = g_exact_centroids.load();
-    if( mode == 1 && per_point_records && g_chains_retry_after.load() > 0 && source->chains_wander.load() > 0 ) { source->chains_wander.fetch_sub( 1 ); mode = 2; }
+    int mode = sw_int( SW_EXACT_CENTROIDS );
+    if( mode == 1 && per_point_records && sw_int( SW_CHAINS_RETRY_AFTER ) > 0 && source->chains_wander.load() > 0 ) { source->chains_wander.fetch_sub( 1 ); mode = 2; }
     StopEdges edge;
     TrShift ts( p0 );
     int rc = icp_align_impl( source, nullptr, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode, false, &edge );
     // (a problem of the slice whose chains gave up: that slice again, its seven sums by pass 2 of the replay — nothing of it was written yet)
     if( rc == ICP_CHAINS_GAVE_UP )
     {
-      source->chains_wander.store( g_chains_retry_after.load() );
+      source->chains_wander.store( sw_int( SW_CHAINS_RETRY_AFTER ) );
       rc = icp_align_impl( source, nullptr, target, T, np, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, 2, false, &edge );
     }
     if( rc == ICP_STOP_EDGE ) rc = icp_stop_guard_rerun( edge, source, nullptr, target, T, T2, max_dist, max_angle, max_iter, fixed_iters, e, it, mode );
@@ -1549,7 +1535,7 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
   // Every problem gets the estimator its own rs_hip_icp_align would (icp_choose), so that its result is that call's bit for bit: the
   // problems within the reference-order range run as one batch (k_icp_faithful), those within the lane chains' range as another
   // (launch_icp_lane_chains), the rest — estimators built for one source per launch — one by one.
-  const int mode = g_exact_centroids.load();
+  const int mode = sw_int( SW_EXACT_CENTROIDS );
   std::vector<int> group[3];
   for( int p = 0; p < n; ++p )
   {
@@ -1592,77 +1578,35 @@ int rs_hip_icp_align_multi( const rs_hip_cloud_t* const* sources, const rs_hip_c
 
 // (diagnostics) problems run again in the reference's order because a stop test of theirs was decided inside the guard, since rs_hip_init
 int64_t rs_hip_icp_stop_guard_redone( void ) { return g_stop_guard_redone.load(); }
-int32_t rs_hip_icp_early_plain( int32_t on )
+// The setters of the switches that have one (rs_switches.h: sw_set — a negative argument only reads; the previous value comes back).
+int32_t rs_hip_icp_early_plain( int32_t on )              { return sw_set( SW_EARLY_PLAIN, on ); }
+int32_t rs_hip_icp_plain_from_records( int32_t on )       { return sw_set( SW_PLAIN_RECORDS, on ); }
+int32_t rs_hip_icp_update_fenced( int32_t on )            { return sw_set( SW_UPDATE_FENCED, on ); }
+float   rs_hip_icp_stop_guard( float guard )              { return sw_set( SW_STOP_GUARD, guard ); }
+int32_t rs_hip_icp_lane_chains_below( int32_t n_points )  { return sw_set( SW_LANE_CHAINS_BELOW, n_points ); }
+int32_t rs_hip_icp_chains_retry_after( int32_t calls )    { return sw_set( SW_CHAINS_RETRY_AFTER, calls ); }
+int32_t rs_hip_icp_reference_order_below( int32_t n_points ) { return sw_set( SW_REF_ORDER_BELOW, n_points ); }
+int32_t rs_hip_icp_replay_below( int32_t n_points )       { return sw_set( SW_REPLAY_BELOW, n_points ); }
+int32_t rs_hip_icp_exact_centroids( int32_t on )          { return sw_set( SW_EXACT_CENTROIDS, on ); }
+int32_t rs_hip_icp_faith_guess( int32_t permille )        { return sw_set( SW_FAITH_GUESS, permille ); }
+int64_t rs_hip_score_scene_space_from( int64_t n_queries ) { return sw_set( SW_SCORE_SCENE_MIN, n_queries ); }
+// The value the library would use now for a name of the table (a flag, or a word that is set: 1); no device needed.
+int rs_hip_switch_get( const char* name, double* value )
 {
-  const int prev = g_early_plain.load();
-  if( on >= 0 ) g_early_plain.store( on ? 1 : 0 );
-  return prev;
+  const int k = sw_find( name );
+  if( k < 0 || !value ) { set_err( "switch_get: %s is no switch of rs_switches.h", name ? name : "(null)" ); return RS_HIP_E_ARG; }
+  *value = sw_value( (SwId)k ).d;
+  return RS_HIP_OK;
 }
-int32_t rs_hip_icp_plain_from_records( int32_t on )
-{
-  const int prev = g_plain_records.load();
-  if( on >= 0 ) g_plain_records.store( on ? 1 : 0 );
-  return prev;
-}
-int32_t rs_hip_icp_update_fenced( int32_t on ) { return icp_update_fenced( on ); }
 void rs_hip_icp_state_layout( int32_t* words_per_problem, int32_t* launch_max_words )
 {
   if( words_per_problem ) *words_per_problem = ICP_STATE_WORDS;
   if( launch_max_words ) *launch_max_words = rs::FillRanges::STATE_MAX;
 }
-float rs_hip_icp_stop_guard( float guard )
-{
-  const float prev = g_stop_guard.load();
-  if( guard >= 0.0f ) g_stop_guard.store( guard );
-  return prev;
-}
-
-int32_t rs_hip_icp_lane_chains_below( int32_t n_points )
-{
-  const int prev = g_lane_below.load();
-  if( n_points >= 0 ) g_lane_below.store( n_points );
-  return prev;
-}
-
 // (diagnostics) of all addends the lane chains have summed since rs_hip_init, how many were added one by one in fp32 (per mille)
 int64_t rs_hip_icp_lane_chains_sequential( void ) { return g_lane_seq_addends.load(); }
 
 int32_t rs_hip_icp_chains_gave_up( void ) { return g_chains_gave_up.load(); }
-
-int32_t rs_hip_icp_chains_retry_after( int32_t calls )
-{
-  const int prev = g_chains_retry_after.load();
-  if( calls >= 0 ) g_chains_retry_after.store( calls );
-  return prev;
-}
-
-int32_t rs_hip_icp_reference_order_below( int32_t n_points )
-{
-  const int prev = g_ref_order_below.load();
-  if( n_points >= 0 ) g_ref_order_below.store( n_points );
-  return prev;
-}
-
-int32_t rs_hip_icp_replay_below( int32_t n_points )
-{
-  const int prev = g_replay_below.load();
-  if( n_points >= 0 ) g_replay_below.store( n_points );
-  return prev;
-}
-
-int32_t rs_hip_icp_exact_centroids( int32_t on )
-{
-  const int prev = g_exact_centroids.load();
-  if( on >= 0 ) g_exact_centroids.store( on > 2 ? 1 : on );
-  return prev;
-}
-
-int32_t rs_hip_icp_faith_guess( int32_t permille )
-{
-  const int prev = g_faith_guess_permille.load();
-  if( permille >= 0 ) g_faith_guess_permille.store( permille );
-  return prev;
-}
 
 int32_t rs_hip_icp_faith_redone( void )
 {
@@ -1823,14 +1767,14 @@ int rs_hip_icp_estimate_pt2pl( const float* pts1, const float* pts2, const float
   L.n_mom_blocks = std::max( 1, std::min( 256, ( n + 255 ) / 256 ) ); L.w_explicit = g_ws.wexp.as<float>();
   // (a single estimator step on the caller's own correspondences: wherever the ICP loop would centre on the reference's chains — the lane
   //  chains' range — this entry point simply runs the reference's order: one call, its cost does not matter, its bits do)
-  const int seq_below = std::max( g_ref_order_below.load(), g_exact_centroids.load() != 0 ? g_lane_below.load() : 0 );
-  if( n <= std::max( seq_below, g_replay_below.load() ) )
+  const int seq_below = std::max( sw_int( SW_REF_ORDER_BELOW ), sw_int( SW_EXACT_CENTROIDS ) != 0 ? sw_int( SW_LANE_CHAINS_BELOW ) : 0 );
+  if( n <= std::max( seq_below, sw_int( SW_REPLAY_BELOW ) ) )
   {
     // the reference's own accumulation order (k_icp_faithful, or its parallel form): solve and pose update on the device too
     if( ( rc = g_ws.faith.ensure( nn * FAITH_REC * 4 ) ) ) return rc;
     L.faith = g_ws.faith.as<float>(); L.by_orig = nullptr; L.err = g_ws.state.as<float>() + 34;
     // (the points are presented untransformed, so the state's pose stays the identity uploaded above and T1 is multiplied in afterwards)
-    if( n <= seq_below || n > g_replay_below.load() ) { ProfScope ps( "icp_moments" ); launch_icp_faithful( L, g_stream ); }
+    if( n <= seq_below || n > sw_int( SW_REPLAY_BELOW ) ) { ProfScope ps( "icp_moments" ); launch_icp_faithful( L, g_stream ); }
     else
     {
       ReplayBufs RB{};
@@ -1862,13 +1806,6 @@ int rs_hip_icp_estimate_pt2pl( const float* pts1, const float* pts2, const float
 // alignment score
 // ------------------------------------------------------------------------------------------
 
-std::atomic<long long> g_score_scene_from{ getenv( "RS_HIP_SCORE_SCENE_MIN" ) ? atoll( getenv( "RS_HIP_SCORE_SCENE_MIN" ) ) : 65536 };
-int64_t rs_hip_score_scene_space_from( int64_t n_queries )
-{
-  const long long prev = g_score_scene_from.load();
-  if( n_queries >= 0 ) g_score_scene_from.store( n_queries );
-  return prev;
-}
 
 // The launches of a batch whose poses are on the device already and whose scores stay there (the calling thread's stream; no
 // copy, no wait): rs_hip_alignment_scores below is this between an upload and a read-back, rs_propose.hip calls it per object and
@@ -1893,17 +1830,16 @@ static int score_poses_device( const rs_hip_cloud_t* object, const rs_hip_cloud_
   L.hist = hist;
   // Scene-space route (rs_score.hip: k_score_scene) for batches on a cell grid that are worth a sort: every query keyed by the
   // scene-aligned block it lands in.  RS_HIP_SCORE_SCENE=0 turns it off, RS_HIP_SCORE_SCENE_MIN sets the batch size it starts at.
-  static const int scene_route = getenv( "RS_HIP_SCORE_SCENE" ) ? atoi( getenv( "RS_HIP_SCORE_SCENE" ) ) : 1;
-  const long long scene_min = g_score_scene_from.load();
-  static const float parent_scale = getenv( "RS_HIP_SCORE_PARENT" ) ? (float)atof( getenv( "RS_HIP_SCORE_PARENT" ) ) : 1.0f;   // parent edge / radius
+  const int scene_route = sw_int( SW_SCORE_SCENE );
+  const long long scene_min = sw_i64( SW_SCORE_SCENE_MIN );
+  const float parent_scale = sw_float( SW_SCORE_PARENT );   // parent edge / radius
   int chunk_poses = 65535;      // the launch grid's y dimension is limited to 65535 poses per launch
   const bool scene_space = scene_route && L.scene.inv_cell > 0.0f &&
                            (long long)n_poses * object->n >= scene_min && object->n < ( 1 << 24 );
   if( scene_space )
   {
     const GridView& g = L.scene;
-    static const int nbin = getenv( "RS_HIP_SCORE_NBIN" ) ? atoi( getenv( "RS_HIP_SCORE_NBIN" ) ) : 1;
-    static const int cull = getenv( "RS_HIP_SCORE_CULL" ) ? atoi( getenv( "RS_HIP_SCORE_CULL" ) ) : 1;
+    const int nbin = sw_int( SW_SCORE_NBIN ), cull = sw_int( SW_SCORE_CULL );
     // the scene grid's box grown by the radius: a query outside has nothing to match ...
     float lo[3] = { g.minx - radius, g.miny - radius, g.minz - radius };
     float hi[3] = { g.minx + g.w * g.cell + radius, g.miny + g.h * g.cell + radius, g.minz + g.d * g.cell + radius };
@@ -1964,7 +1900,7 @@ static int score_poses_device( const rs_hip_cloud_t* object, const rs_hip_cloud_
     // per block): its waves would be no better filled with neighbours than object tiles are, and the sort — more key bits, millions of
     // items — costs more than the searches (level 2: 3.4 ms against 2.8; level 3: 2.7 against 1.85, tools/score_grid_timing.py).  Such
     // batches keep the object-space launch.  (A threshold of 0 queries, as the tests set it, takes the route whatever the density.)
-    static const double density_min = getenv( "RS_HIP_SCORE_SCENE_DENSITY" ) ? atof( getenv( "RS_HIP_SCORE_SCENE_DENSITY" ) ) : 128.0;
+    const double density_min = sw_double( SW_SCORE_SCENE_DENSITY );
     if( scene_min > 0 && (double)n_poses * object->n < density_min * (double)L.sq_n_parents )
     {
       L.sq_key_a = nullptr; chunk_poses = 65535;
@@ -1972,7 +1908,7 @@ static int score_poses_device( const rs_hip_cloud_t* object, const rs_hip_cloud_
     else
     {
       // (counting instead of a radix sort while a table of 2^bits counters is small next to the batch: rs_score.hip, k_score_scatter; RS_HIP_SCORE_COUNTING=0: the radix sort)
-      static const int counting_max_bits = getenv( "RS_HIP_SCORE_COUNTING" ) ? atoi( getenv( "RS_HIP_SCORE_COUNTING" ) ) : 22;
+      const int counting_max_bits = sw_int( SW_SCORE_COUNTING );
       const bool counting = bits <= counting_max_bits;
       const size_t n_bins = ( (size_t)1 << bits ) + 1;
       const size_t tmp_bytes = counting ? build_scan_temp_bytes( n_bins ) : build_sort_temp_bytes( (int)items, bits );
@@ -2009,7 +1945,7 @@ int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t*
   HIP_TRY( hipMemcpyAsync( g_ws.poses.p, poses, (size_t)n_poses * 64, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
   unsigned long long* hist = nullptr;
   thread_local DevBuf histbuf;
-  if( RS_DBG && getenv( "RS_HIP_SCORE_HIST" ) && !histbuf.ensure( 7 * 65 * 8 ) ) { (void)hipMemsetAsync( histbuf.p, 0, 7 * 65 * 8, g_stream ); hist = histbuf.as<unsigned long long>(); }
+  if( RS_DBG && sw_flag( SW_SCORE_HIST ) && !histbuf.ensure( 7 * 65 * 8 ) ) { (void)hipMemsetAsync( histbuf.p, 0, 7 * 65 * 8, g_stream ); hist = histbuf.as<unsigned long long>(); }
   if( ( rc = score_poses_device( object, scene, g_ws.poses.as<float>(), poses, nullptr, n_poses, radius, max_n_neigh, g_ws.scores.as<float>(), hist ) ) ) return rc;
   HIP_TRY( hipMemcpyAsync( scores, g_ws.scores.p, (size_t)n_poses * 4, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
   HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
@@ -2354,8 +2290,8 @@ int rs_hip_radius_search( const rs_hip_cloud_t* target, const float* query, int6
   // tens of thousands of times with a few hundred queries and K = 64, pose_proposal.cpp:115-124).  Short rows of many
   // queries stay with the tiled successive-minima kernel below, whose cost grows with K but whose tiles share their sweeps.
   const int wave_path_max_k = 1024;
-  const long long tiled_from = getenv( "RS_HIP_ROWS_TILED_FROM" ) ? atoll( getenv( "RS_HIP_ROWS_TILED_FROM" ) ) : 4096;      // (read per call: tests switch it)
-  if( k <= wave_path_max_k && ( k >= 16 || nq < tiled_from ) && !getenv( "RS_HIP_NO_ROWS_WAVE" ) )
+  const long long tiled_from = sw_i64( SW_ROWS_TILED_FROM );      // (read per call: tests switch it)
+  if( k <= wave_path_max_k && ( k >= 16 || nq < tiled_from ) && !sw_flag( SW_NO_ROWS_WAVE ) )
   {
     // One upload, one launch, one download, one synchronisation: the call is latency (the unchanged pose_proposal makes
     // ~35 k of them per run).  Queries and the overflow flag travel in one pinned block; counts, distances and indices
@@ -2368,14 +2304,14 @@ int rs_hip_radius_search( const rs_hip_cloud_t* target, const float* query, int6
     int* h_nn = W.h_a.as<int>();
     // Small calls go without the two copies: the pinned blocks are device-visible, the kernel reads the queries from host memory
     // and stores counts and rows straight into it (a few tens of KB over PCIe), so a call is ONE launch and one synchronisation.
-    static const size_t zero_copy_below = getenv( "RS_HIP_ROWS_ZERO_COPY_BELOW" ) ? (size_t)atoll( getenv( "RS_HIP_ROWS_ZERO_COPY_BELOW" ) ) : ( 256u << 10 );
+    const size_t zero_copy_below = (size_t)sw_i64( SW_ROWS_ZERO_COPY_BELOW );
     if( down_words * 4 <= zero_copy_below )
     {
       // (RS_HIP_ROWS_POLL=1, off by default: instead of synchronising the stream the host polls the counts — every wave stores its
       //  row, then, after a system-scope fence, the row's count, which the host pre-set to a sentinel.  3 us less per call, and not
       //  safe: in one of ~60 suite runs a row was read before it had arrived — writes to host memory over PCIe may pass each
       //  other, a fence on the device does not order their ARRIVAL; only the runtime's completion signal does.)
-      static const bool poll = getenv( "RS_HIP_ROWS_POLL" ) != nullptr;
+      const bool poll = sw_flag( SW_ROWS_POLL );
       const int pending = INT_MIN;
       if( poll ) for( int i = 0; i < nq; ++i ) ( (volatile int*)h_nn )[i] = pending;
       { ProfScope ps( "nn_rows" );

@@ -172,7 +172,6 @@ struct ChainBufs
 void   launch_icp_chain_centroids( const IcpLaunch& L, const ChainBufs& B, hipStream_t st );
 void   launch_icp_plain_from_records( const IcpLaunch& L, const ChainBufs& B, hipStream_t st );      // fp64 moments + update, no chains (L.exact_centroids == 0)
 void   launch_icp_plain_from_matches( const IcpLaunch& L, const ChainBufs& B, hipStream_t st );      // the same from m_slot / m_d2 / m_dot of a search without records (k_plain_moments)
-int    icp_update_fenced( int on );      // k_icp_update_wide's hand-over by two full fences again (1), by agent-scope atomics (0, the default); < 0: ask.  Returns the previous value
 int    plain_moment_blocks( int n_tiles );      // ... its workgroups, and partials, per problem: L.n_mom_blocks of that launch
 // the same seven sums for object-sized sources, one wave per chain, any number of (differently sized) problems: B.totals, B.done, B.resolved, B.addends only
 void   launch_icp_lane_chains( const IcpLaunch& L, const ChainBufs& B, hipStream_t st );

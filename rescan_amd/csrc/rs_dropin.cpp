@@ -12,6 +12,7 @@
 
 #include "../../include/rescan_dropin.h"
 #include "../../include/rescan_hip.h"
+#include "rs_switches.h"
 
 #include <chrono>
 #include <cmath>
@@ -33,6 +34,8 @@ static_assert( offsetof(rsd_hash_grid_t, data_buffer) == 64, "data_buffer offset
 static_assert( offsetof(rsd_hash_grid_t, _n_pts) == 112, "_n_pts offset" );
 static_assert( sizeof(rsd_search_desc_t) == 64, "msh_hash_grid_search_desc_t is 64 bytes" );
 
+using namespace rs;
+
 namespace {
 
 // The unchanged apps wait for ~37 k small searches per run: ask librescan_hip.so for busy-waiting completion waits (27 instead of
@@ -47,7 +50,7 @@ void complain( const char* where )
 // RS_DROPIN_STATS=1: where the shim's time went, printed when the process ends (calls / seconds per entry point and route)
 struct Stats
 {
-  bool on = getenv( "RS_DROPIN_STATS" ) != nullptr;
+  bool on = sw_flag( SW_DROPIN_STATS );
   struct Row { const char* name; unsigned long long calls = 0, items = 0; double seconds = 0.0; };
   Row rows[10] = { { "grid init (host index)" }, { "grid device index (lazy)" }, { "radius_search, host path" }, { "radius_search, device path" },
                    { "icp_align" }, { "scores (flat entry)" }, { "labels (flat entry)" }, { "other" },
@@ -125,11 +128,7 @@ uint64_t full_hash( const void* a, const void* b, size_t bytes )
 // object level and every level-2 scan the reference's call sites pass; an in-place edit of any byte is seen.  Larger arrays are
 // keyed by a sample (first and last 64 bytes plus 62 blocks spread over the rest) and the full hash is re-checked on the first
 // and then every kVerifyEvery-th hit; RS_DROPIN_FULL_HASH=1 hashes everything on every call.
-size_t full_hash_below()
-{
-  static const size_t v = getenv( "RS_DROPIN_FULL_HASH" ) ? ~(size_t)0 : getenv( "RS_DROPIN_FULL_HASH_BELOW" ) ? (size_t)atoll( getenv( "RS_DROPIN_FULL_HASH_BELOW" ) ) : ( (size_t)4 << 20 );
-  return v;
-}
+size_t full_hash_below() { return sw_flag( SW_DROPIN_FULL_HASH ) ? ~(size_t)0 : (size_t)sw_i64( SW_DROPIN_FULL_HASH_BELOW ); }
 
 uint64_t sampled_hash( const void* a, const void* b, size_t bytes )
 {
@@ -152,11 +151,7 @@ uint64_t sampled_hash( const void* a, const void* b, size_t bytes )
 // (default 64 KB: every level-2 object of the reference's call sites stays on the full hash) and RS_DROPIN_FULL_HASH_BELOW are keyed by
 // every eighth 64-byte block plus both ends — an edit of 512 consecutive bytes anywhere is seen at once, any edit at the next
 // periodic full-hash check (first hit, then every kVerifyEvery-th), rsd_cache_invalidate / msh_hash_grid_term at once.
-size_t full_hash_small()
-{
-  static const size_t v = getenv( "RS_DROPIN_FULL_HASH" ) ? ~(size_t)0 : getenv( "RS_DROPIN_FULL_HASH_SMALL" ) ? (size_t)atoll( getenv( "RS_DROPIN_FULL_HASH_SMALL" ) ) : ( (size_t)64 << 10 );
-  return v;
-}
+size_t full_hash_small() { return sw_flag( SW_DROPIN_FULL_HASH ) ? ~(size_t)0 : (size_t)sw_i64( SW_DROPIN_FULL_HASH_SMALL ); }
 uint64_t strided_hash( const void* a, const void* b, size_t bytes )
 {
   uint64_t h = 0x2545f4914f6cdd1dull ^ bytes;
@@ -503,7 +498,7 @@ static void hash_grid_init( rsd_hash_grid_t* hg, const float* pts, const int32_t
   // No HIP device: no grid (there is no CPU fallback; every search on it returns 0 neighbours).  RS_DROPIN_INIT_WITHOUT_DEVICE=1
   // is for tests of the failure path on a machine without a GPU: the grid is initialised, and every batched search then
   // fails on the device side exactly as after a runtime error.
-  if( rs_hip_synchronize() != RS_HIP_OK && !getenv( "RS_DROPIN_INIT_WITHOUT_DEVICE" ) ) { complain( "msh_hash_grid_init_3d" ); return; }
+  if( rs_hip_synchronize() != RS_HIP_OK && !sw_flag( SW_DROPIN_INIT_WITHOUT_DEVICE ) ) { complain( "msh_hash_grid_init_3d" ); return; }
   GridHandle* h = new GridHandle();
   h->src = pts; h->dim = dim; h->radius = radius;
   {
@@ -574,7 +569,7 @@ size_t msh_hash_grid_radius_search( const rsd_hash_grid_t* hg, rsd_search_desc_t
 
 static size_t radius_search_3d( GridHandle* h, rsd_search_desc_t* d )
 {
-  const size_t host_queries = getenv( "RS_DROPIN_HOST_QUERIES" ) ? (size_t)atoll( getenv( "RS_DROPIN_HOST_QUERIES" ) ) : 4;      // (read per call: tests switch it)
+  const size_t host_queries = (size_t)sw_i64( SW_DROPIN_HOST_QUERIES );      // (read per call: tests switch it)
   if( d->n_query_pts <= host_queries )
   {
     Timed t( 2, d->n_query_pts );
@@ -613,7 +608,7 @@ size_t msh_hash_grid_knn_search( const rsd_hash_grid_t* hg, rsd_search_desc_t* d
     return 0;
   }
   GridHandle* h = (GridHandle*)hg->data_buffer;
-  const size_t host_queries = getenv( "RS_DROPIN_HOST_QUERIES" ) ? (size_t)atoll( getenv( "RS_DROPIN_HOST_QUERIES" ) ) : 4;      // (as for radius search)
+  const size_t host_queries = (size_t)sw_i64( SW_DROPIN_HOST_QUERIES );      // (as for radius search)
   if( d->n_query_pts > host_queries && d->k <= RS_HIP_KNN_MAX_K )
   {
     rs_hip_knn_grid_t* kg = device_knn_of( h );

@@ -1,6 +1,7 @@
 // librescan_hip device code (gfx950, wave64) — the ICP estimators: fp64 moments, reference-order chains, replay, grid chains (lib/rs/icp.h:136-148,210-298)
 #include "rs_search.h"
 #include "rs_icp.h"
+#include "rs_switches.h"     // sw_int( SW_UPDATE_FENCED ): which hand-over launch_icp_update_wide launches
 #include "rs_tail_dbg.h"      // TD_STAMP: phase stamps of the kernels that end an iteration (diagnostic builds; nothing otherwise)
 #include <atomic>
 #include <cstdlib>
@@ -300,18 +301,11 @@ __global__ __launch_bounds__( BLOCK ) void k_icp_update_wide( IcpLaunch L, int* 
   icp_tail_finish( L, prob, in, m, dbg );
 }
 namespace {
-std::atomic<int> g_update_fenced{ getenv( "RS_HIP_UPDATE_FENCED" ) ? atoi( getenv( "RS_HIP_UPDATE_FENCED" ) ) : 0 };
 void launch_icp_update_wide( const IcpLaunch& L, int* done, hipStream_t st )
 {
-  if( g_update_fenced.load() ) hipLaunchKernelGGL( k_icp_update_wide<true>, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, done );
+  if( sw_int( SW_UPDATE_FENCED ) ) hipLaunchKernelGGL( k_icp_update_wide<true>, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, done );
   else hipLaunchKernelGGL( k_icp_update_wide<false>, dim3( ICP_NMOM, L.n_prob ), dim3( BLOCK ), 0, st, L, done );
 }
-}
-int icp_update_fenced( int on )
-{
-  const int prev = g_update_fenced.load();
-  if( on >= 0 ) g_update_fenced.store( on ? 1 : 0 );
-  return prev;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2705,7 +2699,7 @@ void launch_icp_lane_chains( const IcpLaunch& L, const ChainBufs& B, hipStream_t
 }
 
 // The step WITHOUT the chains: the fp64 moments from the searches' records, centred on their own fp64 centroids (icp_solve without the
-// reference's) — what an early iteration of a scan-sized call runs (rs_api.hip: g_early_plain).  L.exact_centroids must be 0.
+// reference's) — what an early iteration of a scan-sized call runs (rs_api.hip: icp_plain_iterations).  L.exact_centroids must be 0.
 void launch_icp_plain_from_records( const IcpLaunch& L, const ChainBufs& B, hipStream_t st )
 {
   ChainBufs Bq = B; Bq.refresh = 0;
