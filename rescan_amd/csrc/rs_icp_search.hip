@@ -195,6 +195,13 @@ __device__ __forceinline__ void icp_emit( const IcpLaunch& L, int prob, int tile
 #ifndef RS_XCD_MAP
 #define RS_XCD_MAP 1
 #endif
+// The cold launch (k_icp_corr<false>) sweeps its shells culled to the tile's box grown by a ball, rows from the middle outwards, and
+// its rank pass likewise (rs_search.h: cull_tile).  The warm one-sweep launch (k_icp_corr<true>) and the cooperative
+// kernels have none of it — on the latter it was built and measured slower.  Results keep their bits.  RS_ICP_CULL=0: the unculled
+// cold launch (measurements, tools/variant.sh).
+#ifndef RS_ICP_CULL
+#define RS_ICP_CULL 1
+#endif
 // workgroups of phase A's natural part per XCD class (see k_icp_corr)
 // Waves per workgroup of phase A (k_icp_corr).  A workgroup's wave slots and LDS are released when its LAST wave ends, and a
 // warm tile takes its wave 12 us at the median, 17 at the 90th percentile: with four tiles per workgroup a quarter of the slot time
@@ -305,7 +312,7 @@ __global__ __launch_bounds__( PA_WAVES * WAVE, BOUNDED_ONLY ? RS_ICP_WARM_OCC : 
   const int thr_total = (int)( ( (unsigned)min( L.heavy_total, 0xffff ) * sq8 ) >> 8 );
   const uint32_t thr_streamed = ( (unsigned)min( L.heavy_streamed, 0xffff ) * sq8 ) >> 8;
   const uint32_t thr_handoff = ( (unsigned)min( L.heavy_handoff, 0xffff ) * sq8 ) >> 8;
-  Match m = tile_search<true, true, BOUNDED_ONLY>( L.tgt, search, qx, qy, qz, nx, ny, nz, L.radius, L.radius_sq, L.gate_tmin, L.K,
+  Match m = tile_search<true, true, BOUNDED_ONLY, RS_ICP_CULL && !BOUNDED_ONLY>( L.tgt, search, qx, qy, qz, nx, ny, nz, L.radius, L.radius_sq, L.gate_tmin, L.K,
                                lds[wib], lane, L.solo_stages, &handoff, DBG( L ) ? unsettled : nullptr, init, &sweeps, L.by_rows != 0, &streamed, thr_total );
   if( L.heavy_out && lane == 0 )
   {

@@ -848,6 +848,18 @@ __device__ __forceinline__ CellBox cull_cells( const GridView& g, const Cull& c,
   return box_clip( cell_box( g, t, 0.0f ), clip );
 }
 
+// ... and the culling of the ICP's cold launch (tile_search<.., WARM, .., CULL>): the TILE's box grown by the radius.  The box is the
+// one the search starts from anyway and the reach is a constant, so it costs no reduction, and it holds for any subset of the lanes
+// (a lane lies in the tile's box and never looks farther than the radius).  Built from the unsettled lanes' own box and farthest
+// reach (cull_of, or one such group for the lanes with a match and one for those without) it swept a few per cent fewer candidates
+// and measured slower: thirteen and twenty wave reductions ahead of every shell (profiles/r15/ab_icp_cull.txt).
+__device__ __forceinline__ Cull cull_tile( const GridView& g, const TileBounds& t, float radius )
+{
+  const float R = radius + ( 1e-4f * g.cell + 2e-5f );      // (the margin of cull_of)
+  Cull c; c.lx = t.lx; c.hx = t.hx; c.ly = t.ly; c.hy = t.hy; c.lz = t.lz; c.hz = t.hz; c.R2 = R * R;
+  return c;
+}
+
 template <bool GATED, bool WARM = false, bool BOUNDED_ONLY = false, bool CULL = false>
 __device__ __forceinline__ Match tile_search( const GridView& g, bool active,
                                               float qx, float qy, float qz, float nx, float ny, float nz,
@@ -870,10 +882,12 @@ __device__ __forceinline__ Match tile_search( const GridView& g, bool active,
   const bool grid = g.inv_cell > 0.0f;
   const bool all_bounded = WARM && grid && !__any( active & !m.found );
   CellBox full, core, cur, prev;
+  Cull tile_cl{};
   if( all_bounded ) { full.x0 = full.y0 = full.z0 = 0; full.x1 = g.w - 1; full.y1 = g.h - 1; full.z1 = g.d - 1; core = full; }   // only clips reach_box below
   else
   {
     const TileBounds tb = wave_bounds( active, qx, qy, qz );
+    if constexpr( CULL && WARM ) tile_cl = cull_tile( g, tb, radius );
     full = cell_box( g, tb, radius );
     if( box_empty( full ) ) return m;
     core = cell_box( g, tb, 0.0f );
@@ -918,18 +932,29 @@ __device__ __forceinline__ Match tile_search( const GridView& g, bool active,
   bool unsettled = active;
   // (CULL — the scene-space score batch, whose tiles are a few centimetres across: the tile's own cells and the first ring in ONE sweep;
   //  a sweep of a dozen candidates costs its set-up, not its candidates)
-  for( int k = ( CULL && grid ) ? 1 : 0; ; k = k ? 2 * k : 1 )
+  // (CULL of the ICP's cold launch — WARM: the ladder and the boxes of the unculled search, so that no shell visits a cell it did not
+  //  visit before; while a lane it is swept for has no match — it looks the whole radius — the rows of a shell are culled to the tile's
+  //  box grown by a ball and enumerated from the middle outwards.  A shell swept only for lanes with a match is millimetres deep: as it was.
+  //  Exact for the reasons the score route relies on: consider4 takes the minimum in the total order (d², index), whatever the order of
+  //  arrival; a culled cell lies farther than the radius from every lane; seen_closer stays an upper bound of the rank in any order, so
+  //  a rank pass that no longer runs would have confirmed rank < K, and one that runs counts — order-free — inside the match's distance.
+  //  Only fail_max, a maximum over the candidates that were in-bound WHEN MET, may come out smaller: certificates equally valid, not
+  //  bit-identical; what they decide changes no result.)
+  constexpr bool TILE_CULL = CULL && WARM;
+  for( int k = ( CULL && !TILE_CULL && grid ) ? 1 : 0; ; k = k ? 2 * k : 1 )
   {
     cur = grid ? box_grow( core, k, full ) : full;
     Cull cl{};
-    if( CULL && grid ) cl = cull_of( g, unsettled, reach(), qx, qy, qz );
+    bool culled = CULL && grid;
+    if constexpr( TILE_CULL ) { culled = grid && __any( unsettled & !m.found ); cl = tile_cl; }
+    else if( CULL && grid ) cl = cull_of( g, unsettled, reach(), qx, qy, qz );
     // (CULL: the box from the lanes' common box and farthest reach — seven wave reductions instead of thirteen; the rows are clipped to the ball anyway)
-    const CellBox out = !grid ? full : CULL ? cull_cells( g, cl, cur ) : reach_box( g, cur, unsettled, reach(), qx, qy, qz );
+    const CellBox out = !grid ? full : ( CULL && !TILE_CULL ) ? cull_cells( g, cl, cur ) : reach_box( g, cur, unsettled, reach(), qx, qy, qz );
     if( dbg_unsettled && sweeps < 5 ) { dbg_unsettled[4 + 2 * sweeps] = __popcll( __ballot( unsettled ) ); dbg_unsettled[5 + 2 * sweeps] = -(int)streamed; }     // [4 + 2 s]: lanes shell s is swept for, [5 + 2 s]: candidates it streamed
     if( !box_empty( out ) )
     {
       streamed += sweep_shell<GATED>( g, out, prev, have_prev, L, lane, 0, 1, [&]( const float4& X, const float4& Y, const float4& Z, int k4 )
-      { consider4<GATED, WARM>( X, Y, Z, k4, L, qx, qy, qz, nx, ny, nz, tmin, bound, m, seen_closer ); }, 0xffffffffu, CULL && grid, cl );
+      { consider4<GATED, WARM>( X, Y, Z, k4, L, qx, qy, qz, nx, ny, nz, tmin, bound, m, seen_closer ); }, 0xffffffffu, culled, cl );
     }
     if( dbg_unsettled ) { dbg_unsettled[1] = (int)streamed; if( sweeps < 5 ) dbg_unsettled[5 + 2 * sweeps] += (int)streamed; }
     ++sweeps;
@@ -968,7 +993,7 @@ __device__ __forceinline__ Match tile_search( const GridView& g, bool active,
       int rank = 0;
       Cull cl{};
       if( CULL && grid ) cl = cull_of( g, need_rank, reach_of( m, radius ), qx, qy, qz );
-      const CellBox rb = ( CULL && grid ) ? cull_cells( g, cl, cur ) : reach_box( g, cur, need_rank, reach_of( m, radius ), qx, qy, qz );
+      const CellBox rb = ( CULL && !WARM && grid ) ? cull_cells( g, cl, cur ) : reach_box( g, cur, need_rank, reach_of( m, radius ), qx, qy, qz );
       uint32_t rs = 0;
       RankBands rbands = rank_bands( m );
       if( !box_empty( rb ) )
