@@ -1,6 +1,8 @@
 // Host runtime shared by the translation units with entry points of their own (rs_knn.hip, rs_isect.hip, rs_arrange.hip,
-// rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip): what they need from rs_api.hip, a growable buffer, the failure path, a profiling
-// span and the grid size of a launch.  Host only: no kernel file needs it.
+// rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip): what they need from the host side of the C ABI, a growable buffer, the failure
+// path, a profiling span and the grid size of a launch.  Host only: no kernel file needs it.  The api_* functions are defined by the unit
+// that owns what they reach: api_level_workspace / api_cloud_from_level_workspace in rs_rows_api.hip, api_score_poses_device in
+// rs_score.hip, the others in rs_api.hip.
 #pragma once
 #include "../../include/rescan_hip.h"
 #include "rs_device.h"
@@ -10,7 +12,7 @@
 
 namespace rs {
 
-// rs_api.hip's runtime state (defined at its end)
+// the runtime state of the C ABI's host side
 int             api_ready( hipStream_t* st );              // ensure_ready(); *st = the calling thread's stream
 void            api_set_err( const char* what );           // rs_hip_last_error()'s text
 const GridView* api_cloud_view( const struct ::rs_hip_cloud* c );

@@ -1,5 +1,16 @@
 // librescan_hip device code (gfx950, wave64) — the alignment-score batch (apps/pose_proposal/pose_proposal.cpp:93-158)
 #include "rs_search.h"
+#include "rs_api.h"
+#include "rs_host.h"
+#include "rs_math.h"
+#include "rs_switches.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
 
 namespace rs {
 
@@ -328,4 +339,200 @@ void launch_score( const ScoreLaunch& L, hipStream_t st )
   hipLaunchKernelGGL( k_score_final, dim3( L.n_poses ), dim3( BLOCK ), 0, st, L );
 }
 
+} // namespace rs
+
+// ------------------------------------------------------------------------------------------
+// alignment score
+// ------------------------------------------------------------------------------------------
+// (host side: the launches of a batch and the entry points over them; runtime state, clouds and profiling through rs_api.h)
+
+using namespace rs;
+
+namespace {
+struct ScoreWorkspace
+{
+  DevBuf poses, score_part, scores, queue, queue_count;                                   // (queue: the tiles a search launch hands to the cooperative kernel)
+  DevBuf sq_ka, sq_kb, sq_va, sq_vb, sq_pq, sq_tmp, sq_hist;                             // ... scene-space batches: keys / payloads (ping-pong), per-query terms, sort workspace
+};
+thread_local ScoreWorkspace g_ws;
+} // namespace
+
+// The launches of a batch whose poses are on the device already and whose scores stay there (the calling thread's stream; no
+// copy, no wait): rs_hip_alignment_scores below is this between an upload and a read-back, rs_propose.hip calls it per object and
+// level.  Where queries can fall — the scene-space route's lattice — comes from the poses where the host has them (h_poses), else
+// from query_box (lo[3], hi[3]; null: the scene's box).  object->n >= 1, n_poses >= 1.
+static int score_poses_device( const rs_hip_cloud_t* object, const rs_hip_cloud_t* scene, const float* d_poses, const float* h_poses,
+                               const float* query_box, int32_t n_poses, float radius, int32_t max_n_neigh, float* d_scores,
+                               unsigned long long* hist )
+{
+  int rc;
+  const float* poses = h_poses;
+  const int n_tiles = object->qview.n_tiles;
+  if( ( rc = g_ws.score_part.ensure( (size_t)n_poses * n_tiles * 8 ) ) ||
+      ( rc = g_ws.queue.ensure( (size_t)std::min( n_poses, 65535 ) * n_tiles * 4 ) ) || ( rc = g_ws.queue_count.ensure( 4 ) ) )
+    return rc;
+  ScoreLaunch L{};
+  L.scene = scene->view; L.scene.evals = g_prof ? g_evals : nullptr; L.obj = object->qview;
+  L.poses = d_poses; L.radius_sq = radius_sq_of( radius ); L.gate_tmin = score_gate_threshold();
+  L.K = max_n_neigh; L.sigma = (double)radius; L.part = g_ws.score_part.as<double>(); L.scores = d_scores;
+  L.queue = g_ws.queue.as<int>(); L.queue_count = g_ws.queue_count.as<int>();
+  L.solo_stages = handoff_threshold( (long long)n_tiles * n_poses );
+  L.hist = hist;
+  // Scene-space route (rs_score.hip: k_score_scene) for batches on a cell grid that are worth a sort: every query keyed by the
+  // scene-aligned block it lands in.  RS_HIP_SCORE_SCENE=0 turns it off, RS_HIP_SCORE_SCENE_MIN sets the batch size it starts at.
+  const int scene_route = sw_int( SW_SCORE_SCENE );
+  const long long scene_min = sw_i64( SW_SCORE_SCENE_MIN );
+  const float parent_scale = sw_float( SW_SCORE_PARENT );   // parent edge / radius
+  int chunk_poses = 65535;      // the launch grid's y dimension is limited to 65535 poses per launch
+  const bool scene_space = scene_route && L.scene.inv_cell > 0.0f &&
+                           (long long)n_poses * object->n >= scene_min && object->n < ( 1 << 24 );
+  if( scene_space )
+  {
+    const GridView& g = L.scene;
+    const int nbin = sw_int( SW_SCORE_NBIN ), cull = sw_int( SW_SCORE_CULL );
+    // the scene grid's box grown by the radius: a query outside has nothing to match ...
+    float lo[3] = { g.minx - radius, g.miny - radius, g.minz - radius };
+    float hi[3] = { g.minx + g.w * g.cell + radius, g.miny + g.h * g.cell + radius, g.minz + g.d * g.cell + radius };
+    L.sq_lox = lo[0]; L.sq_hix = hi[0]; L.sq_loy = lo[1]; L.sq_hiy = hi[1]; L.sq_loz = lo[2]; L.sq_hiz = hi[2];
+    // ... and the parent lattice only spans where queries CAN fall: the object's box under every pose, cut to that box (fewer key
+    // bits: a radix pass less).  The object's own grid spans its bounding box; a brute-layout object falls back to the scene's box.
+    const GridView& og = object->view;
+    if( !poses && query_box )
+    {
+      for( int a = 0; a < 3; ++a )
+      {
+        lo[a] = std::max( lo[a], query_box[a] ); hi[a] = std::min( hi[a], query_box[3 + a] );
+        if( hi[a] < lo[a] ) hi[a] = lo[a];
+      }
+    }
+    else if( poses && og.inv_cell > 0.0f )
+    {
+      float qlo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, qhi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
+      const float omin[3] = { og.minx, og.miny, og.minz }, omax[3] = { og.minx + og.w * og.cell, og.miny + og.h * og.cell, og.minz + og.d * og.cell };
+      bool finite = true;
+      for( int p = 0; p < n_poses; ++p )
+        for( int c = 0; c < 8; ++c )
+        {
+          const float x = ( c & 1 ) ? omax[0] : omin[0], y = ( c & 2 ) ? omax[1] : omin[1], z = ( c & 4 ) ? omax[2] : omin[2];
+          const float* M = poses + (size_t)p * 16;
+          for( int a = 0; a < 3; ++a )
+          {
+            const float v = M[a] * x + M[4 + a] * y + M[8 + a] * z + M[12 + a];
+            if( !std::isfinite( v ) ) finite = false;
+            qlo[a] = std::min( qlo[a], v ); qhi[a] = std::max( qhi[a], v );
+          }
+        }
+      if( finite )
+        for( int a = 0; a < 3; ++a )
+        {
+          const float pad = 1e-3f + 1e-5f * std::max( std::fabs( qlo[a] ), std::fabs( qhi[a] ) );      // (rounding of the corner transforms; the key only groups anyway)
+          lo[a] = std::max( lo[a], qlo[a] - pad ); hi[a] = std::min( hi[a], qhi[a] + pad );
+          if( hi[a] < lo[a] ) hi[a] = lo[a];
+        }
+    }
+    // parent edge: the radius, as a whole number of cells (a coarser grid: its cell); doubled until the lattice has < 2^24 / 64 parents
+    float parent = g.cell * std::max( 1.0f, roundf( parent_scale * radius / g.cell ) );
+    const int fine_bits = 6;
+    for( ;; parent *= 2.0f )
+    {
+      L.sq_dpx = (int)ceilf( ( hi[0] - lo[0] ) / parent ) + 1; L.sq_dpy = (int)ceilf( ( hi[1] - lo[1] ) / parent ) + 1; L.sq_dpz = (int)ceilf( ( hi[2] - lo[2] ) / parent ) + 1;
+      const double total = (double)L.sq_dpx * L.sq_dpy * L.sq_dpz;
+      if( total < (double)( 1 << 24 ) ) { L.sq_n_parents = (int)total; break; }
+    }
+    L.sq_ox = lo[0]; L.sq_oy = lo[1]; L.sq_oz = lo[2];
+    int bits = 0;
+    while( ( 1ll << bits ) <= ( (long long)L.sq_n_parents << fine_bits ) ) ++bits;      // the "nothing to match" key n_parents << fine_bits sorts last
+    L.sq_bits = bits; L.sq_fine_bits = fine_bits; L.sq_inv_fine = 4.0f / parent; L.sq_nbin = nbin ? 1 : 0; L.sq_cull = cull;
+    chunk_poses = (int)std::min<long long>( 65535, std::max<long long>( 1, ( 1ll << 30 ) / object->n ) );
+    const size_t items = (size_t)std::min( chunk_poses, n_poses ) * object->n;
+    // The route pays where MANY queries share a block — a proposal's verification, a refinement's neighbourhood: the bench's 256 poses put
+    // ~650 queries into each of ~4 000 blocks.  The grid search of a pyramid level scatters its poses over the whole room (a dozen queries
+    // per block): its waves would be no better filled with neighbours than object tiles are, and the sort — more key bits, millions of
+    // items — costs more than the searches (level 2: 3.4 ms against 2.8; level 3: 2.7 against 1.85, tools/score_grid_timing.py).  Such
+    // batches keep the object-space launch.  (A threshold of 0 queries, as the tests set it, takes the route whatever the density.)
+    const double density_min = sw_double( SW_SCORE_SCENE_DENSITY );
+    if( scene_min > 0 && (double)n_poses * object->n < density_min * (double)L.sq_n_parents )
+    {
+      L.sq_key_a = nullptr; chunk_poses = 65535;
+    }
+    else
+    {
+      // (counting instead of a radix sort while a table of 2^bits counters is small next to the batch: rs_score.hip, k_score_scatter; RS_HIP_SCORE_COUNTING=0: the radix sort)
+      const int counting_max_bits = sw_int( SW_SCORE_COUNTING );
+      const bool counting = bits <= counting_max_bits;
+      const size_t n_bins = ( (size_t)1 << bits ) + 1;
+      const size_t tmp_bytes = counting ? build_scan_temp_bytes( n_bins ) : build_sort_temp_bytes( (int)items, bits );
+      if( ( rc = g_ws.sq_ka.ensure( items * 4 ) ) || ( rc = g_ws.sq_kb.ensure( items * 4 ) ) || ( rc = g_ws.sq_va.ensure( items * 4 ) ) ||
+          ( rc = g_ws.sq_vb.ensure( items * 4 ) ) || ( rc = g_ws.sq_pq.ensure( items * 8 ) ) || ( rc = g_ws.sq_tmp.ensure( tmp_bytes ) ) ||
+          ( counting && ( rc = g_ws.sq_hist.ensure( n_bins * 4 ) ) ) )
+        return rc;
+      L.sq_hist = counting ? g_ws.sq_hist.as<uint32_t>() : nullptr;
+      L.sq_key_a = g_ws.sq_ka.as<uint32_t>(); L.sq_key_b = g_ws.sq_kb.as<uint32_t>(); L.sq_val_a = g_ws.sq_va.as<uint32_t>(); L.sq_val_b = g_ws.sq_vb.as<uint32_t>();
+      L.sq_pq = g_ws.sq_pq.as<double>(); L.sq_tmp = g_ws.sq_tmp.p; L.sq_tmp_bytes = g_ws.sq_tmp.cap;
+    }
+  }
+  for( int p0 = 0; p0 < n_poses; p0 += chunk_poses )
+  {
+    ScoreLaunch Lp = L;
+    Lp.n_poses = std::min( chunk_poses, n_poses - p0 );
+    Lp.poses = L.poses + (size_t)p0 * 16; Lp.part = L.part + (size_t)p0 * n_tiles; Lp.scores = L.scores + p0;
+    ProfScope ps( "nn_score" );
+    launch_score( Lp, g_stream );
+  }
+  return RS_HIP_OK;
+}
+
+extern "C" {
+
+int rs_hip_alignment_scores( const rs_hip_cloud_t* object, const rs_hip_cloud_t* scene,
+                             const float* poses, int32_t n_poses, float radius, int32_t max_n_neigh,
+                             float* scores )
+{
+  int rc = ensure_ready(); if( rc ) return rc;
+  if( !object || !scene || !object->has_nor || !scene->has_nor || !poses || !scores || n_poses < 0 || max_n_neigh <= 0 )
+  { set_err( "alignment_scores: bad arguments" ); return RS_HIP_E_ARG; }
+  if( n_poses == 0 ) return RS_HIP_OK;
+  if( object->n == 0 ) { for( int p = 0; p < n_poses; ++p ) scores[p] = NAN; return RS_HIP_OK; }   // 0/0, pose_proposal.cpp:156
+  if( ( rc = g_ws.poses.ensure( (size_t)n_poses * 64 ) ) || ( rc = g_ws.scores.ensure( (size_t)n_poses * 4 ) ) ) return rc;
+  HIP_TRY( hipMemcpyAsync( g_ws.poses.p, poses, (size_t)n_poses * 64, hipMemcpyHostToDevice, g_stream ), RS_HIP_E_RUNTIME );
+  unsigned long long* hist = nullptr;
+  thread_local DevBuf histbuf;
+  if( RS_DBG && sw_flag( SW_SCORE_HIST ) && !histbuf.ensure( 7 * 65 * 8 ) ) { (void)hipMemsetAsync( histbuf.p, 0, 7 * 65 * 8, g_stream ); hist = histbuf.as<unsigned long long>(); }
+  if( ( rc = score_poses_device( object, scene, g_ws.poses.as<float>(), poses, nullptr, n_poses, radius, max_n_neigh, g_ws.scores.as<float>(), hist ) ) ) return rc;
+  HIP_TRY( hipMemcpyAsync( scores, g_ws.scores.p, (size_t)n_poses * 4, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
+  HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
+  if( hist && n_poses >= 256 )
+  {
+    std::vector<unsigned long long> h( 7 * 65 );
+    (void)hipMemcpy( h.data(), hist, h.size() * 8, hipMemcpyDeviceToHost );
+    unsigned long long all = 0; for( size_t k = 0; k < 6 * 65; ++k ) all += h[k];
+    {
+      unsigned long long ns = 0, nl = 0, b[5] = { 0, 0, 0, 0, 0 };
+      for( int u = 0; u <= 64; ++u ) { ns += h[6 * 65 + u]; nl += h[6 * 65 + u] * u; b[u <= 4 ? 0 : u <= 8 ? 1 : u <= 16 ? 2 : u <= 32 ? 3 : 4] += h[6 * 65 + u]; }
+      if( ns ) fprintf( stderr, "[rs_hip score hist] scene-space searches %llu, %.1f lanes each | by lanes 1-4: %4.1f %%  5-8: %4.1f %%  9-16: %4.1f %%  17-32: %4.1f %%  33-64: %4.1f %%\n", ns, (double)nl / ns,
+                        100.0 * b[0] / ns, 100.0 * b[1] / ns, 100.0 * b[2] / ns, 100.0 * b[3] / ns, 100.0 * b[4] / ns );
+    }
+    fprintf( stderr, "[rs_hip score hist] candidates streamed %llu (rows 0-4: shells, by the lanes the shell is swept for; row 5: the rank pass, by the lanes that need their rank)\n", all );
+    for( int sh = 0; sh < 6; ++sh )
+    {
+      unsigned long long t = 0, b[5] = { 0, 0, 0, 0, 0 };      // lanes the shell is swept for: 1-4, 5-8, 9-16, 17-32, 33-64
+      for( int u = 0; u <= 64; ++u ) { t += h[sh * 65 + u]; b[u <= 4 ? 0 : u <= 8 ? 1 : u <= 16 ? 2 : u <= 32 ? 3 : 4] += h[sh * 65 + u]; }
+      if( t ) fprintf( stderr, "[rs_hip score hist]   shell %d: %5.1f %% of all | by unsettled lanes 1-4: %4.1f %%  5-8: %4.1f %%  9-16: %4.1f %%  17-32: %4.1f %%  33-64: %4.1f %%\n", sh,
+                       100.0 * (double)t / (double)all, 100.0 * b[0] / (double)t, 100.0 * b[1] / (double)t, 100.0 * b[2] / (double)t, 100.0 * b[3] / (double)t, 100.0 * b[4] / (double)t );
+    }
+  }
+  return RS_HIP_OK;
+}
+
+int64_t rs_hip_score_scene_space_from( int64_t n_queries ) { return sw_set( SW_SCORE_SCENE_MIN, n_queries ); }
+
+} // extern "C"
+
+namespace rs {
+int api_score_poses_device( const rs_hip_cloud* object, const rs_hip_cloud* scene, const float* d_poses, const float* query_box,
+                            int32_t n_poses, float radius, int32_t max_n_neigh, float* d_scores )
+{
+  if( !object->has_nor || !scene->has_nor || object->n <= 0 || n_poses <= 0 ) { set_err( "score_poses_device: bad arguments" ); return RS_HIP_E_ARG; }
+  return score_poses_device( object, scene, d_poses, nullptr, query_box, n_poses, radius, max_n_neigh, d_scores, nullptr );
+}
 } // namespace rs

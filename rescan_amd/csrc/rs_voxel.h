@@ -1,5 +1,5 @@
 // The reference's voxel grid (lib/rs/intersect.h:59-109) as the coverage code and the arrangement code (rs_rows.hip,
-// rs_arrange.hip, rs_api.hip) share it: the grid of a box, the cell of a point, the coverage object.
+// rs_arrange.hip, rs_rows_api.hip) share it: the grid of a box, the cell of a point, the coverage object.
 #pragma once
 #include "rs_device.h"
 

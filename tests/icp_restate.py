@@ -32,7 +32,7 @@ def next_max_dist(md):
 
 
 def _stat_scales(max_dist):
-    """rs_api.hip: icp_set_radius — the fixed-point scales of the searches' Σd², Σd⁴ (r² of the float radius)."""
+    """rs_icp_api.hip: icp_set_radius — the fixed-point scales of the searches' Σd², Σd⁴ (r² of the float radius)."""
     r2 = float(f32(max_dist) * f32(max_dist))
     e1 = 35 - (np.frexp(r2)[1] - 1)
     e2 = 35 - (np.frexp(r2 * r2)[1] - 1)

@@ -163,7 +163,7 @@ def test_headline_sharded_route_is_bit_identical(capi, bench_mod, headline):
 
 def test_many_problem_batches_take_the_narrow_cooperative_tiles(capi, bench_mod):
     """Round 6: a batch of more than eight ICP problems runs its cooperative searches at 4 waves per queued tile from 32 768 tiles in
-    all, at 2 from 131 072 (rs_api.hip: icp_coop_waves — such launches are throughput-bound; 512 refines: 33.8 -> 28.9 ms per step).
+    all, at 2 from 131 072 (rs_icp_api.hip: icp_coop_waves — such launches are throughput-bound; 512 refines: 33.8 -> 28.9 ms per step).
     Ten start poses of the headline scan (156 k tiles: 2 waves) — the eight of the units fixture, two of them twice — end where the
     reference's ten iterations end and where the single calls end, bit for bit; nine start poses of every fourth point of the scan
     (~35 k tiles: 4 waves) where their single calls end."""

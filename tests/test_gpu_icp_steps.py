@@ -38,7 +38,7 @@ I4 = np.eye(4, dtype=np.float32).ravel()
 MA = np.float32(np.deg2rad(60.0))
 POLICY_TOL = 2e-5
 
-# ---- the estimator policy (include/rescan_hip.h; rs_api.hip) at the default thresholds -------------------
+# ---- the estimator policy (include/rescan_hip.h; rs_icp_api.hip) at the default thresholds -------------------
 REF_ORDER_BELOW = 16384          # rs_hip_icp_reference_order_below
 LANE_BELOW = 65536               # rs_hip_icp_lane_chains_below (batches)
 LANE_SINGLE_CAP = 28672          # ... a call with one problem: the grid chains from here on

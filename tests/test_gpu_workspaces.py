@@ -4,7 +4,10 @@ next call after a refusal.  Every comparison is exact: against the project's hos
 tests/isect_restate.py, tests/resample_restate.py, rs_hip_shuffle_plan, numpy, tests/planes_restate.py) or, for the coverage
 extensions, against the same call made first after rs_hip_arrange_release.
 Each test runs in one child process under its own time limit, so that the thread's workspaces start empty whatever ran before;
-nothing here provokes a fault or a HIP error: every refusal is one of arguments."""
+nothing here provokes a fault or a HIP error: every refusal is one of arguments.
+The second half does the same for the four host units of the C ABI proper (rs_api.hip, rs_icp_api.hip, rs_score.hip,
+rs_rows_api.hip: DevBuf, ProfScope), each with a workspace of its own: calls of different units alternate while their buffers grow,
+against the committed fixtures with the parity suite's own comparisons (tests/test_gpu_parity.py)."""
 import subprocess
 import sys
 
@@ -152,8 +155,8 @@ def refused(code, what, f, *a, **k):
 """
 
 
-def run_child(body, limit=120):
-    out = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-c", PRELUDE + body, ROOT], capture_output=True, text=True)
+def run_child(body, limit=120, prelude=PRELUDE):
+    out = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, "-c", prelude + body, ROOT], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), (out.returncode, out.stdout[-3000:], out.stderr[-3000:])
     return out.stdout
 
@@ -256,3 +259,179 @@ for name, (call, want, sizes) in UNITS.items():
     same(call(sizes[0]), before[name])
 print("ok")
 """)
+
+
+# ---- the four host units of the C ABI: every step IS a case of tests/test_gpu_parity.py, called on its fixture ----
+API_PRELUDE = r"""
+import ctypes as C, os, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+from rescan_amd import capi
+import test_gpu_parity as TP                     # its test functions are called as they are: no comparison is restated here
+from conftest import coverage_case, label_case, load_golden
+from oracle.pyoracle import LEVEL_VOXEL, level_max_n_neigh
+capi.init(0)
+F = np.float32
+sd = load_golden("scene.npz")                    # (conftest.gscene, which is a fixture and cannot be called here)
+gscene = dict(points=sd["points"], normals=sd["normals"],
+              objects=[dict(pos=sd[f"obj{i}_pos"], nor=sd[f"obj{i}_nor"], pose=sd["obj_pose"][i], class_idx=int(sd["obj_class"][i]),
+                            uidx=int(sd["obj_uidx"][i])) for i in range(int(sd["n_obj"]))])
+pts, nor = gscene["points"], gscene["normals"]
+clouds = {r: capi.Cloud(pts, nor, cell_size=2 * r) for r in (0.05, 0.1)}              # test_gpu_parity.scene_clouds
+clouds[0.075] = capi.Cloud(pts, nor)
+objs = [capi.Cloud(o["pos"], o["nor"], cell_size=0.1) for o in gscene["objects"]]
+scene_clouds = (clouds, objs)
+
+# the parity case, then the call's bits (what a repeated call is compared with)
+def scores(fname, scene_route=False):
+    (TP.test_scores_scene_space_route_vs_golden if scene_route else TP.test_scores_vs_golden)(capi, scene_clouds, fname + ".npz")
+    g = load_golden(fname + ".npz")
+    prev = capi.score_scene_space_from(0) if scene_route else None
+    try:
+        return [capi.alignment_scores(objs[int(g["obj"])], clouds[cell], g["poses"], 0.1, int(g["k"])) for cell in (0.05, 0.1)]
+    finally:
+        if scene_route:
+            capi.score_scene_space_from(prev)
+
+def icp(fname):
+    TP.test_icp_align_vs_golden(capi, gscene, scene_clouds, fname + ".npz")
+    g = load_golden(fname + ".npz")
+    md = float(g["max_dist"])
+    err, T, iters = capi.icp_align(objs[int(g["obj"])], clouds[round(md, 3)], g["T1"], g["T2"], md, g["max_angle"])
+    return [T, F(err), np.int32(iters)]
+
+def rows(fname):
+    TP.test_rows_vs_golden(capi, gscene, fname + ".npz")
+    g = load_golden(fname + ".npz")
+    return list(capi.radius_search(clouds[0.05], g["query"], float(g["radius"]), int(g["k"]))[:3])
+
+def coverage_objects():
+    d, cobjs, static, arrangements = coverage_case(gscene)
+    cov = capi.Coverage(d["bbox_min"], d["bbox_max"], pts, d["quality"], 0.05, 0.5)
+    cc = [capi.Cloud(p, np.zeros_like(p)) for p in cobjs]
+    return cov, [[(cc[k], pose, static[k]) for k, pose in plc] for plc in arrangements]
+
+def same(got, want):
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        g, w = np.ascontiguousarray(g), np.ascontiguousarray(w)
+        assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), (k, g.dtype, w.dtype, g.shape, w.shape)
+"""
+
+
+# (as tests/conftest.py: torch initialises its copy of the HIP runtime before librescan_hip.so loads the system's)
+TORCH_FIRST = r"""
+import torch
+torch.cuda.init()
+"""
+
+
+def test_api_units_regrow_next_to_each_other():
+    """One thread, one sequence: score, ICP, score, rows, edges, rows, level, labels, coverage, the estimator entry point, rows, score
+    (through the scene-space route), ICP — the units that shared buffers before each had a workspace of its own (queue / queue_count:
+    ICP and score; rd2 / ridx / rnn: rows and edges; the tile buffer: rows and the estimator entry point; lvl_samples: level and
+    labels) alternate, and the later call of a unit is the larger or the same.  Every result is its fixture's as the parity suite
+    demands; a repeated call returns the bits of its first occurrence."""
+    run_child(r"""
+s1 = scores("scores_chair1_k32")
+i1 = icp("icp_chair1_refine")
+scores("scores_table0_k64")
+r1 = rows("rows_k8_r005")
+TP.test_neighborhood_vs_golden(capi, gscene)                      # (neighborhood_obj0 and the other three)
+rows("rows_k64_r010")
+TP.test_level_builder_vs_golden(capi, gscene)
+TP.test_level_cloud_built_on_the_device(capi, None, gscene)       # (level gather -> cloud construction, across two units)
+TP.test_labels_vs_golden(capi, gscene, scene_clouds, "labels_mixed.npz")
+TP.test_coverage_vs_golden(capi, gscene)
+from oracle.pyoracle import Oracle
+TP.test_icp_estimate_vs_oracle(capi, Oracle(), gscene)
+same(rows("rows_k8_r005"), r1)
+same(scores("scores_chair1_k32", scene_route=True), s1)
+same(icp("icp_chair1_refine"), i1)
+print("ok")
+""", prelude=API_PRELUDE)
+
+
+def test_label_state_outlives_calls_of_other_units():
+    """Two partials of the placement loop written to device memory (rs_hip_label_partial_device returns without a synchronisation,
+    its placements still uploading from the unit's pinned block), a score call and a rows call in between, then the ordered fold:
+    the labels and distances of rs_hip_assign_labels over the same placements, exactly (labels_ties: every distance tie of the
+    fixture is decided by the order)."""
+    run_child(r"""
+d, lobjs, plcs = label_case(gscene, "labels_ties.npz")
+oc = [capi.Cloud(o["pos"], o["nor"], cell_size=0.1) for o in lobjs]
+scene = clouds[0.05]
+ns, n = scene.n, len(plcs)
+order = [int(k) for k in d["order"]]
+poses = np.stack([plcs[k]["pose"] for k in order]); pobj = [oc[plcs[k]["object_idx"]] for k in order]
+first_static = next((k for k, oi in enumerate(order) if lobjs[plcs[oi]["object_idx"]]["is_static"]), 0)
+radii = [0.05 if k < first_static else np.float32(1.5) * np.float32(0.05) for k in range(n)]
+want_l = np.zeros(ns, np.int8); want_m = np.full(ns, 1e9, F)
+capi.assign_labels(scene, poses, pobj, radii, want_l, want_m)
+assert (want_l == d["labels"]).all() and (want_m == d["min_dists"]).all()          # (the fixture's, too: test_labels_vs_golden's sharded route)
+assert len(set(want_l.tolist())) > 3
+# per part: min_dists float32[ns], then labels int8[ns] (rescan_amd/dist.py's layout)
+stride = (5 * ns + 255) // 256 * 256
+dev = torch.empty(2 * stride, dtype=torch.uint8, device="cuda")
+half = n // 2
+for r, (p0, p1) in enumerate(((0, half), (half, n))):
+    base = dev.data_ptr() + r * stride
+    capi.label_partial_device(scene, poses[p0:p1], pobj[p0:p1], radii[p0:p1], p0, base, base + 4 * ns)
+scores("scores_chair1_k32")
+rows("rows_k8_r005")
+mo = np.array([r * stride // 4 for r in range(2)], np.int64); lo = np.array([r * stride + 4 * ns for r in range(2)], np.int64)
+got_l, got_m = capi.fold_label_partials_device(dev.data_ptr(), mo, lo, ns, query_order_of=scene)
+assert got_l.tobytes() == want_l.tobytes() and got_m.tobytes() == want_m.tobytes()
+print("ok")
+""", prelude=TORCH_FIRST + API_PRELUDE)
+
+
+def test_api_spans_are_booked_as_before():
+    """One call per moved entry point under rs_hip_profile_enable, the profile reset in between: the names each books and how often.
+    A ProfScope that lost its launch in the move, or a span now booked by two units, changes a count."""
+    print(run_child(r"""
+# spans per call, taken from the parent commit (one rs_api.hip, one workspace) by running this body on its library
+BOOKED = dict(
+    alignment_scores=dict(nn_score=1),
+    assign_labels=dict(nn_label=1),
+    radius_search=dict(nn_rows=1),
+    compute_neighborhood=dict(nn_rows=1, edges=1),
+    level_samples=dict(level_neighbours=2, level_rounds=1),
+    coverage_scores=dict(coverage=1),
+    icp_align=dict(nn_icp=7, icp_moments=7),
+)
+NAMES = ("nn_score", "nn_label", "label_fold", "nn_rows", "edges", "level_neighbours", "level_rounds", "coverage", "nn_icp", "icp_moments")
+gs, gr, gi = (load_golden(f + ".npz") for f in ("scores_chair1_k32", "rows_k64_r010", "icp_chair1_refine"))
+d, lobjs, plcs = label_case(gscene, "labels_ties.npz")
+oc = [capi.Cloud(o["pos"], o["nor"], cell_size=0.1) for o in lobjs]
+cov, batch = coverage_objects()
+lab = np.zeros(len(pts), np.int8); mind = np.full(len(pts), 1e9, F)
+bare = capi.Cloud(pts, None)
+md = float(gi["max_dist"])
+CALLS = dict(
+    alignment_scores=lambda: capi.alignment_scores(objs[int(gs["obj"])], clouds[0.1], gs["poses"], 0.1, int(gs["k"])),
+    assign_labels=lambda: capi.assign_labels(clouds[0.05], np.stack([p["pose"] for p in plcs]), [oc[p["object_idx"]] for p in plcs], [0.05] * len(plcs), lab, mind),
+    radius_search=lambda: capi.radius_search(clouds[0.05], gr["query"], float(gr["radius"]), int(gr["k"])),
+    compute_neighborhood=lambda: capi.compute_neighborhood(objs[0]),
+    level_samples=lambda: capi.level_samples(bare, LEVEL_VOXEL[2], level_max_n_neigh(2)),
+    coverage_scores=lambda: cov.scores(batch),
+    icp_align=lambda: capi.icp_align(objs[int(gi["obj"])], clouds[round(md, 3)], gi["T1"], gi["T2"], md, gi["max_angle"]),
+)
+for call in CALLS.values():
+    call()                                         # outside the profile: buffers, first launches
+read = {}
+capi.profile_enable(True)
+try:
+    for name, call in CALLS.items():
+        capi.profile_reset()
+        call()
+        read[name] = {k: capi.profile_read(k) for k in NAMES}
+finally:
+    capi.profile_enable(False)
+print({name: {k: v[0] for k, v in r.items() if v[0]} for name, r in read.items()})
+for name, r in read.items():
+    for k, (n, ms) in r.items():
+        assert n == BOOKED[name].get(k, 0), (name, k, n)
+        assert np.isfinite(ms) and ms >= 0.0 and (n > 0 or ms == 0.0), (name, k, ms)
+print("ok")
+""", prelude=API_PRELUDE))

@@ -8,7 +8,8 @@ cd "$(dirname "$0")/../rescan_amd"
 tag=$1; shift
 F="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fno-slp-vectorize -fPIC -Wall -Wno-unused-function"
 objs=""
-for tu in rs_icp_search rs_icp_estimate rs_score rs_rows rs_api; do
+units=$(python -c "import build; print(' '.join(s[:-4] for s in build.SOURCES if s != 'rs_build.hip'))")      # (the library's own list: rescan_amd/build.py)
+for tu in $units; do
   /opt/rocm/bin/hipcc $F "$@" -c csrc/$tu.hip -o /tmp/${tu}_$tag.o &
   objs="$objs /tmp/${tu}_$tag.o"
 done
