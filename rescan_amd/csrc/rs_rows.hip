@@ -663,7 +663,9 @@ __device__ __forceinline__ float edge_weight( const EdgeLaunch& L, float d2, flo
     while( e > 0 ) { if( e & 1 ) r *= b; e >>= 1; if( e ) b *= b; }
     norm_cost = (float)r;
   }
-  else norm_cost = powf( c, L.angle_exp );
+  // (any other exponent: the double pow, rounded once — like the host's powf, which computes in double.  The device's own
+  //  powf is good to 1 ulp and differed from the host's in the last bit on 5 to 12 % of a room's edges.)
+  else norm_cost = (float)pow( (double)c, (double)L.angle_exp );
   return dist_cost * norm_cost;
 }
 

@@ -779,7 +779,7 @@ def test_neighborhood_exponents_and_large(capi, oracle):
     pts, nor = s["points"][:40000].copy(), s["normals"][:40000].copy()
     c = capi.Cloud(pts, nor)
     n = len(pts)
-    # integer exponents are evaluated exactly-then-rounded; fractional ones go through the device pow/powf
+    # integer exponents are evaluated exactly-then-rounded; fractional ones go through the device's double pow, rounded once
     for de, ae, exact in ((2.0, 3.0, True), (15.0, 16.0, True), (1.5, 0.5, False)):
         a, b, w = capi.compute_neighborhood(c, 8, 0.0025, de, ae)
         wa, wb, ww = oracle.compute_neighborhood(pts, nor, 8, 0.0025, de, ae)
