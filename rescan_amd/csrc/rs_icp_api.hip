@@ -514,7 +514,23 @@ void icp_debug_after( IcpCtx& cx, int n_src, int n, int i, float max_dist )
   auto pr = [&]( const char* tag, size_t k ) { if( rows.empty() ) return; k = std::min( k, rows.size() - 1 );
     fprintf( stderr, "[rs_hip dbg]   coop %s: %.1f us (setup %.1f, shell k=2 %.1f, full shell %.1f, rest %.1f), wave-0 streamed %llu cand, searching lanes %llu, unmatched %llu\n", tag, rows[k][0] / 100.0,
              ( rows[k][3] & 0xffff ) / 100.0, ( ( rows[k][3] >> 16 ) & 0xffff ) / 100.0, ( ( rows[k][3] >> 32 ) & 0xffff ) / 100.0, ( rows[k][3] >> 48 ) / 100.0,
-             rows[k][1], rows[k][2] & 0xff, rows[k][2] >> 8 ); };
+             rows[k][1], rows[k][2] & 0xff, ( rows[k][2] >> 8 ) & 0xff ); };
+  // cell rows per sweep (the first three of a tile; 0: no such sweep) and row-table loads per tile, over the queued tiles
+  {
+    std::vector<unsigned> v[4];
+    for( const auto& r : rows )
+    {
+      for( int s = 0; s < 3; ++s ) { const unsigned n = (unsigned)( ( r[2] >> ( 16 + 14 * s ) ) & 0x3fff ); if( n ) v[s].push_back( n ); }
+      v[3].push_back( (unsigned)( r[2] >> 58 ) );
+    }
+    const char* what[4] = { "cell rows of sweep 1", "cell rows of sweep 2", "cell rows of sweep 3", "row-table loads per tile" };
+    for( int s = 0; s < 4; ++s )
+    {
+      if( v[s].empty() ) continue;
+      std::sort( v[s].begin(), v[s].end() );
+      fprintf( stderr, "[rs_hip dbg]   coop %s: p50 %u, p90 %u, max %u (%zu tiles)\n", what[s], v[s][v[s].size() / 2], v[s][v[s].size() * 9 / 10], v[s].back(), v[s].size() );
+    }
+  }
   unsigned long long cat[4]; (void)hipMemcpy( cat, cx.L.dbg + 6 * (size_t)cx.n_waves, 32, hipMemcpyDeviceToHost );
   if( RS_DBG >= 2 ) fprintf( stderr, "[rs_hip dbg]   unmatched lanes: skipped by certificate %llu, freshly certified %llu, rank-rejected %llu, loose-band only %llu\n", cat[0], cat[1], cat[2], cat[3] );
   pr( "p10", rows.size() / 10 ); pr( "p50", rows.size() / 2 ); pr( "p90", rows.size() * 9 / 10 ); pr( "p99", rows.size() * 99 / 100 ); pr( "max", rows.size() - 1 );

@@ -358,7 +358,7 @@ __global__ __launch_bounds__( PA_WAVES * WAVE, BOUNDED_ONLY ? RS_ICP_WARM_OCC : 
 // Returns whether some lane had to search without a starting candidate (the tile is "not bounded": worth a workgroup again
 // next iteration).  Ends with a barrier: the merge slots may be reused at once.
 template <int NW>
-__device__ __forceinline__ bool icp_coop_tile( const IcpLaunch& L, const Xform& T1, int prob, int tile, WaveLds& lds, CoopLds<NW>& coop,
+__device__ __forceinline__ bool icp_coop_tile( const IcpLaunch& L, const Xform& T1, int prob, int tile, WaveLds& lds, CoopLds<NW>& coop, RowTable<NW>* table,
                                                unsigned long long& s_skip, int wib, int lane, int dbg_slot )
 {
   const int i = (int)L.src.tiles[tile] + lane;
@@ -376,8 +376,9 @@ __device__ __forceinline__ bool icp_coop_tile( const IcpLaunch& L, const Xform& 
   __syncthreads();
   const bool search = active & !( ( s_skip >> lane ) & 1ull );
   uint32_t streamed = 0;
+  unsigned long long rows_word = 0;
   Match m = coop_search<true, NW, true>( L.tgt, search, qx, qy, qz, nx, ny, nz, L.radius, L.radius_sq, L.gate_tmin, L.K,
-                               lds, coop, wib, lane, init, DBG( L ) ? &streamed : nullptr, DBG( L ) ? stamps : nullptr );
+                               lds, coop, wib, lane, init, DBG( L ) ? &streamed : nullptr, DBG( L ) ? stamps : nullptr, table, DBG( L ) ? &rows_word : nullptr );
   if( DBG( L ) && wib == 0 && dbg_slot >= 0 )
   {
     const int n_search = __popcll( __ballot( search ) ), n_unm = __popcll( __ballot( search & !m.found ) );
@@ -385,9 +386,10 @@ __device__ __forceinline__ bool icp_coop_tile( const IcpLaunch& L, const Xform& 
     {
       unsigned long long* d = DBG( L ) + 2 * (size_t)L.src.n_tiles + 4 * (size_t)dbg_slot;
       const unsigned long long t_end = wall_clock64();
-      // [0] total | [1] streamed | lanes | phases packed: setup, shell 1, shell 2, rest (each 16 bits, ticks of 10 ns)
+      // [0] total | [1] streamed | [2] searching lanes 8 bits, unmatched 8, cell rows of sweeps 1, 2, 3 (the last may be the rank pass) 14 each, table loads of all sweeps from bit 58
+      // | [3] phases packed: setup, shell 1, shell 2, rest (each 16 bits, ticks of 10 ns)
       auto clip = []( unsigned long long v ) { return v > 0xffffull ? 0xffffull : v; };
-      d[0] = t_end - t_begin; d[1] = streamed; d[2] = (unsigned long long)n_search | ( (unsigned long long)n_unm << 8 );
+      d[0] = t_end - t_begin; d[1] = streamed; d[2] = (unsigned long long)n_search | ( (unsigned long long)n_unm << 8 ) | ( ( rows_word & 0x3ffffffffffull ) << 16 ) | ( ( rows_word >> 42 > 63 ? 63ull : rows_word >> 42 ) << 58 );
       d[3] = clip( stamps[0] - t_begin ) | ( clip( stamps[1] - stamps[0] ) << 16 ) | ( clip( stamps[2] - stamps[1] ) << 32 ) | ( clip( t_end - stamps[2] ) << 48 );
     }
   }
@@ -399,7 +401,10 @@ __device__ __forceinline__ bool icp_coop_tile( const IcpLaunch& L, const Xform& 
 
 // Phase B: one workgroup per queued tile, whole box, chunks shared by its waves.
 #ifndef RS_COOP_OCC
-#define RS_COOP_OCC 5      // waves per SIMD the cooperative kernel's register allocation aims at (96 VGPRs: no spills; 6 = 80 VGPRs spilt 56 B per lane for no gain in time)
+// waves per SIMD the cooperative kernel's register allocation aims at.  sweep_shell's form: 5 = 96 VGPRs, no spills (6 = 80 VGPRs spilt
+// 56 B per lane for no gain in time).  sweep_stream's: 4 = 128 VGPRs, of which it takes 100 to 110 — measured faster than the same
+// code held to 96 (no spills there either with one chunk in flight; two and three spill 8 and 24 to 40 B per lane at 96).
+#define RS_COOP_OCC ( RS_COOP_STREAM ? 4 : 5 )
 #endif
 template <int NW>
 __global__ __launch_bounds__( NW * WAVE, RS_COOP_OCC ) void k_icp_corr_coop( IcpLaunch L )
@@ -407,6 +412,12 @@ __global__ __launch_bounds__( NW * WAVE, RS_COOP_OCC ) void k_icp_corr_coop( Icp
   RS_CHAIN_SETPRIO();
   __shared__ WaveLds lds[NW];
   __shared__ CoopLds<NW> coop;
+#if RS_COOP_STREAM
+  __shared__ RowTable<NW> s_table;      // (4 / 8 KB at 4 / 8 waves: five coop<4> workgroups of 24 KB, three coop<8> of 47 KB per CU)
+  RowTable<NW>* const table = &s_table;
+#else
+  RowTable<NW>* const table = nullptr;      // (coop_search sweeps with sweep_shell)
+#endif
   __shared__ unsigned long long s_skip;
   const int prob = blockIdx.y;
   if( L.active[prob] == 0 ) return;
@@ -421,7 +432,7 @@ __global__ __launch_bounds__( NW * WAVE, RS_COOP_OCC ) void k_icp_corr_coop( Icp
   for( int b = blockIdx.x; b < n_queued; b += gridDim.x )
   {
     const int tile = L.coop_all ? b : L.queue[(size_t)L.tile_off + b];
-    icp_coop_tile<NW>( L, T1, prob, tile, lds[wib], coop, s_skip, wib, lane, b );
+    icp_coop_tile<NW>( L, T1, prob, tile, lds[wib], coop, table, s_skip, wib, lane, b );
   }
 }
 

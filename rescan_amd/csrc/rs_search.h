@@ -43,6 +43,7 @@
 
 #include "rs_device.h"
 #include "rs_math.h"
+#include "rs_rowtable.h"
 #include <cfloat>
 #include <climits>
 #include <algorithm>
@@ -489,6 +490,132 @@ __device__ __forceinline__ uint32_t sweep_shell( const GridView& g, const CellBo
       c0 = cn;
     }
     wave_lds_fence();
+  }
+  if( g.evals && lane == 0 ) L.evals += evaluated;       // (flushed by the kernel's EvalScope)
+  return streamed;
+}
+
+// The shell sweep of NW COOPERATING waves (the ICP's queued tiles, k_icp_corr_coop): the shell is enumerated ONCE per workgroup.
+// sweep_shell walks a shell in batches of 64 cell rows, each batch a chain of exposed round trips — cell_start, prefix sum, first
+// chunk — that every one of the NW waves repeats for all rows; a queued tile's whole-box sweep is two to three such batches with a
+// chunk or two per wave in each, i.e. nothing but those round trips.  Here wave w, lane l describes row 64 w + l of a table in
+// shared memory (NW x 64 rows load their cell_start pairs in one round trip, each lane computes its own row only), each wave scans
+// its own block of 64, the NW block totals are exchanged through LDS and one barrier closes the table; the candidates of ALL rows of
+// the table then form one stream, dealt to the waves in chunks of 64 (chunk c to wave c mod NW) with the loads of a wave's next
+// RS_COOP_PREFETCH chunks in flight while it evaluates one.  A shell of more rows than the table holds takes super-batches of
+// NW x 64 rows.  The index arithmetic is rs_rowtable.h's (checked on the host: tests/host/rowtable_check.cpp).
+// Same rows, same candidates, same order within the stream as sweep_shell's; how the stream is cut into chunks and dealt to the
+// waves differs, so what a wave meets — and with it seen_closer and fail_max, never the merged match — may differ.
+#ifndef RS_COOP_STREAM
+#define RS_COOP_STREAM 1        // 0: the cooperative ICP kernels sweep with sweep_shell, as before (A/B: tools/variant.sh)
+#endif
+#ifndef RS_COOP_PREFETCH
+#define RS_COOP_PREFETCH 1      // chunks of a wave in flight while it evaluates one (1: sweep_shell's lookahead; 2 and 3 measured slower)
+#endif
+template <int NW>
+struct RowTable
+{
+  uint32_t seg_a[NW * WAVE], len_a[NW * WAVE], seg_b[NW * WAVE], pre[NW * WAVE];     // rs_rowtable.h
+  uint32_t block_total[NW];
+};
+template <bool WITH_NOR, int NW, int DEPTH, class F>
+__device__ __forceinline__ uint32_t sweep_stream( const GridView& g, const CellBox& out, const CellBox& in, bool in_valid,
+                                                  WaveLds& L, RowTable<NW>& T, int lane, int wib, F&& f )
+{
+  static_assert( DEPTH >= 1 && DEPTH <= 4, "chunks in flight" );
+  const int ny = out.y1 - out.y0 + 1, nz = out.z1 - out.z0 + 1;
+  const int n_rows = ny * nz;                      // (of the box every wave of the workgroup holds identically: so is every barrier below)
+  const float inv_ny = 1.0f / (float)ny;
+  uint32_t streamed = 0, evaluated = 0;
+  const int n_sb = rt_super_batches( n_rows, NW );
+  for( int sb = 0; sb < n_sb; ++sb )
+  {
+    const int e = wib * WAVE + lane;
+    // this lane's (y,z) row of cells: sweep_shell's arithmetic for an unculled shell, rows with r ascending (written out here and not
+    // in a function of its own: with its four results behind pointers the compiler merged the two piece loads and kept them on the stack)
+    const int r = rt_row_of_entry( sb, NW, e );
+    uint32_t sa = 0, la = 0, sb_ = 0, lb = 0;
+    if( r < n_rows )
+    {
+      int rz = (int)( (float)r * inv_ny );                   // r / ny, off by at most one: see sweep_shell
+      rz -= ( rz * ny > r ) ? 1 : 0;
+      rz += ( ( rz + 1 ) * ny <= r ) ? 1 : 0;
+      const int y = out.y0 + ( r - rz * ny ), z = out.z0 + rz;
+      const uint32_t* cs = g.cell_start + (size_t)( z * g.h + y ) * g.w;
+      const bool inside = in_valid && y >= in.y0 && y <= in.y1 && z >= in.z0 && z <= in.z1;
+      const int cx0 = out.x0, cx1 = out.x1;
+      if( !inside ) { sa = cs[cx0]; la = cs[cx1 + 1] - sa; }
+      else
+      {
+        // the row minus in's x-range (which may stick out of, or miss, out's)
+        const int a1 = min( in.x0 - 1, cx1 ), b0 = max( in.x1 + 1, cx0 );
+        if( a1 >= cx0 ) { sa = cs[cx0]; la = cs[a1 + 1] - sa; }
+        if( b0 <= cx1 ) { sb_ = cs[b0]; lb = cs[cx1 + 1] - sb_; }
+      }
+    }
+    const uint32_t incl = wave_scan( la + lb, lane );
+    // The table is free for this super-batch: n_sb derives from `out`, which is merged data, so all waves come here the same number of
+    // times.  (The FIRST super-batch needs no such barrier: every sweep is followed by a barrier of coop_search's merges before the next.)
+    if( sb > 0 ) __syncthreads();
+    T.seg_a[e] = sa; T.len_a[e] = la; T.seg_b[e] = sb_; T.pre[e] = incl - ( la + lb );
+    if( lane == WAVE - 1 ) T.block_total[wib] = incl;
+    // the table is closed: reached once per super-batch by every wave (same n_sb, no exit from the loop)
+    __syncthreads();
+    uint32_t blk[NW];
+    const uint32_t total = (uint32_t)uni( (int)rt_block_offsets<NW>( T.block_total, blk ) );
+#pragma unroll
+    for( int w = 0; w < NW; ++w ) blk[w] = (uint32_t)uni( (int)blk[w] );      // (wave-uniform: scalar registers, compared as such in every fetch)
+    streamed += total;
+
+    // (the normal's fourth word is never read: twelve bytes per candidate in flight, and a register less per slot of the ring)
+    // (a candidate's position in the cloud waits in the wave's own LDS, in the piece arrays that this sweep leaves unused, not in a
+    //  register of the ring: written and read back by the same lane, so the wave's LDS order is all it needs)
+    auto fetch = [&]( uint32_t c0, float4& P, float3& N, uint32_t* slot_of )
+    {
+      const uint32_t j = c0 + lane;
+      P = make_float4( FLT_MAX, FLT_MAX, FLT_MAX, 0.0f ); N = make_float3( 0.0f, 0.0f, 0.0f );
+      uint32_t src = 0;
+      if( j < total )
+      {
+        src = rt_source<NW>( blk, T.pre, T.seg_a, T.len_a, T.seg_b, j );
+        P = g.pos[src];
+        if( WITH_NOR ) N = *reinterpret_cast<const float3*>( &g.nor[src] );
+      }
+      slot_of[lane] = src;
+    };
+    uint32_t* const slots[4] = { L.seg_a, L.len_a, L.seg_b, L.pre };
+    const uint32_t stride = rt_stride( NW );
+    uint32_t c0 = rt_first( wib );
+    float4 P[DEPTH]; float3 N[DEPTH];
+#pragma unroll
+    for( int d = 0; d < DEPTH; ++d ) { if( c0 + (uint32_t)d * stride < total ) fetch( c0 + (uint32_t)d * stride, P[d], N[d], slots[d] ); }
+    while( c0 < total )
+    {
+#pragma unroll
+      for( int d = 0; d < DEPTH; ++d )      // (slot d of the ring, a compile-time index: the ring stays in registers)
+      {
+        if( c0 >= total ) break;
+        L.px[lane] = P[d].x; L.py[lane] = P[d].y; L.pz[lane] = P[d].z; L.pidx[lane] = __float_as_int( P[d].w );
+        if( WITH_NOR ) { L.nx[lane] = N[d].x; L.ny[lane] = N[d].y; L.nz[lane] = N[d].z; }
+        L.slot[lane] = slots[d][lane];
+        wave_lds_fence();
+        const uint32_t cn = c0 + (uint32_t)DEPTH * stride;
+        if( cn < total ) fetch( cn, P[d], N[d], slots[d] );      // in flight, with the DEPTH - 1 chunks before it, during the loop below
+        const uint32_t cnt = ( total - c0 < WAVE ) ? ( total - c0 ) : WAVE;
+        const uint32_t cnt4 = ( cnt + 3u ) & ~3u;
+        evaluated += cnt;
+#pragma unroll 1
+        for( uint32_t k = 0; k < cnt4; k += 4 )
+        {
+          const float4 X = *reinterpret_cast<const float4*>( &L.px[k] );
+          const float4 Y = *reinterpret_cast<const float4*>( &L.py[k] );
+          const float4 Z = *reinterpret_cast<const float4*>( &L.pz[k] );
+          f( X, Y, Z, (int)k );
+        }
+        wave_lds_fence();
+        c0 += stride;
+      }
+    }
   }
   if( g.evals && lane == 0 ) L.evals += evaluated;       // (flushed by the kernel's EvalScope)
   return streamed;
@@ -1034,9 +1161,21 @@ __device__ __forceinline__ Match coop_search( const GridView& g, bool active,
                                               float qx, float qy, float qz, float nx, float ny, float nz,
                                               float radius, float radius_sq, float tmin, int K,
                                               WaveLds& L, CoopLds<NW>& C, int wib, int lane, Match m /* starting candidate, see tile_search */,
-                                              uint32_t* dbg_streamed = nullptr, unsigned long long* dbg_t = nullptr )
+                                              uint32_t* dbg_streamed = nullptr, unsigned long long* dbg_t = nullptr,
+                                              RowTable<NW>* T = nullptr /* WARM (the ICP's kernels): the workgroup's row table, see sweep_stream */,
+                                              unsigned long long* dbg_rows = nullptr /* out: cell rows of the first three sweeps, 14 bits each | table loads << 42 */ )
 {
+  // the ICP's instantiation enumerates each shell once per workgroup (sweep_stream); the score batch's sweeps as before
+  constexpr bool STREAM = WARM && RS_COOP_STREAM;
   uint32_t streamed = 0;
+  unsigned long long rows_word = 0; int n_noted = 0;
+  auto note_rows = [&]( const CellBox& b )
+  {
+    const unsigned long long rows = (unsigned long long)( ( b.y1 - b.y0 + 1 ) * ( b.z1 - b.z0 + 1 ) );
+    if( n_noted < 3 ) rows_word |= ( rows > 0x3fffull ? 0x3fffull : rows ) << ( 14 * n_noted );
+    ++n_noted;
+    rows_word += ( STREAM ? (unsigned long long)rt_super_batches( (int)rows, NW ) : ( rows + WAVE - 1 ) / WAVE ) << 42;
+  };
   int dbg_k = 0;
   if( dbg_t ) dbg_t[dbg_k++] = wall_clock64();
   const TileBounds tb = wave_bounds( active, qx, qy, qz );
@@ -1067,8 +1206,13 @@ __device__ __forceinline__ Match coop_search( const GridView& g, bool active,
     // only the part of the shell within reach of a still-unsettled lane (see tile_search); identical in every wave
     const CellBox out = ( g.inv_cell > 0.0f ) ? reach_box( g, cur, unsettled, reach_of( m, radius ), qx, qy, qz ) : full;
     if( !box_empty( out ) )
-    streamed += sweep_shell<GATED>( g, out, prev, have_prev, L, lane, wib, NW, [&]( const float4& X, const float4& Y, const float4& Z, int k4 )
-    { consider4<GATED, WARM>( X, Y, Z, k4, L, qx, qy, qz, nx, ny, nz, tmin, bound, m, seen_closer ); } );
+    {
+      auto step = [&]( const float4& X, const float4& Y, const float4& Z, int k4 )
+      { consider4<GATED, WARM>( X, Y, Z, k4, L, qx, qy, qz, nx, ny, nz, tmin, bound, m, seen_closer ); };
+      if( dbg_rows ) note_rows( out );
+      if constexpr( STREAM ) streamed += sweep_stream<GATED, NW, RS_COOP_PREFETCH>( g, out, prev, have_prev, L, *T, lane, wib, step );
+      else streamed += sweep_shell<GATED>( g, out, prev, have_prev, L, lane, wib, NW, step );
+    }
     if( dbg_t && dbg_k < 7 ) dbg_t[dbg_k++] = wall_clock64();
     // merge the per-lane bests of the waves; every wave continues with the merged best
     C.m_d2[wib][lane] = m.d2; C.m_idx[wib][lane] = m.idx; C.m_dot[wib][lane] = m.dot; C.m_slot[wib][lane] = m.found ? m.slot : -1;
@@ -1104,11 +1248,17 @@ __device__ __forceinline__ Match coop_search( const GridView& g, bool active,
       const CellBox rb = reach_box( g, cur, need_rank, reach_of( m, radius ), qx, qy, qz );
       RankBands rbands = rank_bands( m );
       if( !box_empty( rb ) )
-      sweep_shell<false>( g, rb, rb, false, L, lane, wib, NW, [&]( const float4& X, const float4& Y, const float4& Z, int k4 )
       {
-        if( WARM ) { const int c = precede4_bands( X, Y, Z, k4, L, qx, qy, qz, radius_sq, m.d2, m.idx, rbands ); rank += need_rank ? c : 0; }
-        else rank += need_rank ? precede4( X, Y, Z, k4, L, qx, qy, qz, radius_sq, m.d2, m.idx ) : 0;
-      } );
+        auto count = [&]( const float4& X, const float4& Y, const float4& Z, int k4 )
+        {
+          if( WARM ) { const int c = precede4_bands( X, Y, Z, k4, L, qx, qy, qz, radius_sq, m.d2, m.idx, rbands ); rank += need_rank ? c : 0; }
+          else rank += need_rank ? precede4( X, Y, Z, k4, L, qx, qy, qz, radius_sq, m.d2, m.idx ) : 0;
+        };
+        if( dbg_rows ) note_rows( rb );
+        // (rb comes from the merged matches: the same box, and the same barriers inside the sweep, in every wave)
+        if constexpr( STREAM ) sweep_stream<false, NW, RS_COOP_PREFETCH>( g, rb, rb, false, L, *T, lane, wib, count );
+        else sweep_shell<false>( g, rb, rb, false, L, lane, wib, NW, count );
+      }
       __syncthreads();                             // everyone is done reading the counts
       C.m_cnt[wib][lane] = rank;
       if( WARM ) C.m_bands[wib][lane] = min( rbands.c1, 31 ) | ( min( rbands.c2, 31 ) << 8 ) | ( min( rbands.c3, 31 ) << 16 ) | ( min( rbands.c4, 31 ) << 24 );
@@ -1126,6 +1276,7 @@ __device__ __forceinline__ Match coop_search( const GridView& g, bool active,
     }
   }
   if( dbg_streamed ) *dbg_streamed = streamed;
+  if( dbg_rows ) *dbg_rows = rows_word;
   if( dbg_t ) { while( dbg_k < 7 ) dbg_t[dbg_k++] = wall_clock64(); }
   return m;
 }

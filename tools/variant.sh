@@ -3,6 +3,8 @@
 # RS_HIP_LIB=<path> (rescan_amd/capi.py).   usage: tools/variant.sh <tag> [-DNAME=VALUE ...]
 #   tools/variant.sh dbg -DRS_DBG=1            per-tile timers of the search kernels (RS_HIP_DEBUG_CYCLES)
 #   tools/variant.sh taildbg -DRS_TAIL_DBG=1   phase stamps of k_plain_moments / k_icp_update_wide, rs_hip_debug_tail_dump (csrc/rs_tail_dbg.h)
+#   tools/variant.sh s0 -DRS_COOP_STREAM=0     the cooperative ICP kernels with sweep_shell instead of the row table and stream (rs_search.h)
+#   tools/variant.sh s2 -DRS_COOP_PREFETCH=2 [-DRS_COOP_OCC=5]   chunks of a wave in flight / the kernels' waves-per-SIMD target
 set -e
 cd "$(dirname "$0")/../rescan_amd"
 tag=$1; shift
