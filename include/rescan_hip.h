@@ -804,7 +804,11 @@ void rs_hip_mat4_mul( const float* a, const float* b, float* out );
  * (msh_rotate, msh_vec_math.h:2091-2092) — evaluated on the host for n arguments, so that a CPU test can hold it
  * against the libm of the machine (no GPU needed). */
 void rs_hip_sincosf_model( const float* x, int64_t n, float* sin_out, float* cos_out );
-/* icp_estimate_rigid_xform_pt2pl (lib/rs/icp.h:210-298) on host arrays (device reduction) */
+/* icp_estimate_rigid_xform_pt2pl (lib/rs/icp.h:210-298) on host arrays (device reduction).  The estimator is chosen by n and the
+ * thresholds above, as for rs_hip_icp_align.  Weights that vanish (their sum <= 1e-7: all zero, for instance): the reference's
+ * estimator has no guard of its own there — it divides by the sum and returns NaN — while its caller, icp_align, tests the sum
+ * first and keeps the pose (icp.h:466-470).  This entry point does what the caller does, whichever estimator runs: T1 is left as
+ * it came, *err = 0 and RS_HIP_OK comes back. */
 int  rs_hip_icp_estimate_pt2pl( const float* pts1, const float* pts2, const float* nor2,
                                 const float* weights, int32_t n, float* T1, float* err );
 

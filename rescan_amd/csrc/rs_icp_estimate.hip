@@ -2466,15 +2466,16 @@ __global__ __launch_bounds__( BLOCK ) void k_chain_walk_and_moments( IcpLaunch L
 // one wave per chain, any number of problems side by side (grid.y = problem, each bound to its own source: icp_bind).
 //
 // The grid chains above pay five launches and a forecast machinery to spread ONE chain over the chip; a source of a few
-// ten thousand points does not need that.  A wave takes 256 addends at a time, four consecutive ones per lane, and applies the
+// ten thousand points does not need that.  A wave takes a stretch of 1 024 addends at a time, sixteen consecutive ones per lane
+// (LC_PER_LANE; four stretches' loads in flight: LC_DEPTH), and applies the
 // same fact — inside a binade the sum is an integer sum — directly: every addend scaled by 1 / ulp( s ) and rounded to
-// nearest-even is what it adds to the mantissa; the four of a lane are prefixed in registers, the lanes by one DPP scan; if every
+// nearest-even is what it adds to the mantissa; the sixteen of a lane are prefixed in registers, the lanes by one DPP scan; if every
 // partial mantissa stays inside the binade (one grid step clear of its ends, as the records above) and no addend sits exactly
-// half way between two grid points, the 256 additions ARE that integer addition.  Otherwise the stretch is cut at the first
-// lane that does not fit: the lanes before it are taken by the integers, that lane's four addends are added in fp32 one
+// half way between two grid points, the 1 024 additions ARE that integer addition.  Otherwise the stretch is cut at the first
+// lane that does not fit: the lanes before it are taken by the integers, that lane's sixteen addends are added in fp32 one
 // after the other — the reference's own operation, so a change of binade, a tie, a sum that is zero, denormal or not finite
 // need no case of their own — and the rest is tried again from the new value.  A sum that hovers (coordinates of both
-// signs) makes little headway per attempt; then the fp32 stretch doubles, up to 16 lanes: the worst case is the plain
+// signs) makes little headway per attempt; then the fp32 stretch doubles, up to four lanes: the worst case is the plain
 // sequential sum plus an attempt per 64 addends.  Nothing is given up and nothing is forecast: the result is the
 // sequential sum for any input (tests/test_gpu_parity.py: test_lane_chains_are_the_sequential_sums).
 //   k_lane_chains_and_moments   workgroups 0-1: the seven walks (a wave each); the rest: the fp64 moments of a quarter block of

@@ -99,12 +99,13 @@ def seq_centroids(p1, p2, w):
     if len(w) == 0:
         z = np.zeros(3, np.float32)
         return z, z, f32(0)
-    tw = np.add.accumulate(w, dtype=np.float32)[-1]
+    zero = np.zeros(1, np.float32)                                      # (the chains start at +0: 0 + -0 = +0, where accumulate alone would keep x[0])
+    tw = np.add.accumulate(np.concatenate([zero, w]), dtype=np.float32)[-1]
     inv = f32(1.0) / tw
     c = []
     for P in (p1, p2):
         P = np.asarray(P, np.float32)
-        s = np.array([np.add.accumulate(P[:, k] * w, dtype=np.float32)[-1] for k in range(3)], np.float32)
+        s = np.array([np.add.accumulate(np.concatenate([zero, P[:, k] * w]), dtype=np.float32)[-1] for k in range(3)], np.float32)
         c.append((s * inv).astype(np.float32))
     return c[0], c[1], f32(tw)
 
