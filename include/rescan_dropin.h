@@ -221,6 +221,18 @@ int   rsd_coverage_extensions( void* coverage, const rsd_vec3_t* const* base_pos
                                const int32_t* base_static, int32_t n_base,
                                const rsd_vec3_t* const* cand_pos, const int32_t* cand_n, const rsd_mat4_t* cand_poses, int32_t n_cand,
                                float* scores );
+/* The coverage term of rsao_simulated_annealing's 25 000 arrangements (arrangement_optimization.cpp:388 ff.) without a device call
+ * per iteration (rs_hip_coverage_footprints, rs_hip_footprints_scores).  Before the loop, ONE rsd_coverage_footprints over every
+ * placement the loop can hold — each proposal of each dynamic object of the scene, then the placements of the starting arrangement:
+ * obj_* / poses / is_static as for rsd_coverage_score.  Returns a handle (host memory), NULL on failure.  Inside
+ * rsao__compute_scene_coverage_score, rsd_footprints_score( handle, members, n ) is the score of the arrangement whose placements
+ * are members[0 .. n) — indices into the list given to rsd_coverage_footprints, found by (object_idx, the pose's 64 bytes), NOT by
+ * pose_idx, which the move action leaves stale (:513-516) — bit for bit; < 0 on a bad index.  It touches no device.  One thread
+ * at a time per handle. */
+void* rsd_coverage_footprints( void* coverage, const rsd_vec3_t* const* obj_pos, const int32_t* obj_n, const rsd_mat4_t* poses,
+                               const int32_t* is_static, int32_t n_plc );
+float rsd_footprints_score( void* footprints, const int32_t* members, int32_t n_members );
+void  rsd_footprints_destroy( void* footprints );
 /* rsao_compute_scene_saliency (arrangement_optimization.cpp:1109-1160, 1292-1295; apps/segment_transfer/main.cpp:337) for one
  * scene: quality[i] replaces scn->qualities[0][i].  bbox = the scene cloud's, voxel_size = 0.15f (main.cpp:327); obj_* =
  * rsdb->objects[o].shape level 2; proposal k = (object, rsdb->proposed_poses[scene][object][pose], rsdb_is_object_static);

@@ -54,7 +54,7 @@ int         rs_hip_switch_get( const char* name, double* value );
 /* Per-kernel timing with HIP events recorded on the launch stream.  While enabled, each
  * launch of a hot kernel is bracketed by an event pair; rs_hip_profile_read() synchronises
  * and returns launch count and summed milliseconds for kernel `name`
- * ("nn_icp", "icp_moments", "nn_score", "nn_label", "nn_rows", "edges", "coverage", "isect").  The name "candidates" is
+ * ("nn_icp", "icp_moments", "nn_score", "nn_label", "nn_rows", "edges", "coverage", "isect", "footprints").  The name "candidates" is
  * not a kernel: its launch count is the number of candidates the search kernels staged and evaluated
  * since the last reset (each of them by the 64 query lanes of its wave) — SURVEY.md §8d's second figure. */
 int         rs_hip_profile_enable( int on );
@@ -590,10 +590,52 @@ int  rs_hip_coverage_extensions( rs_hip_coverage_t* c,
 int32_t rs_hip_coverage_lds_budget( int32_t bytes );
 /* (diagnostics) Candidates the process scored on the LDS route and on the slab route since the last reset. */
 void    rs_hip_coverage_extension_routes( int64_t* lds, int64_t* slab, int32_t reset );
-/* rs_hip_coverage_extensions and rs_hip_scene_saliency keep their device and pinned buffers per calling thread between calls (a bit
+/* rs_hip_coverage_extensions, rs_hip_coverage_footprints and rs_hip_scene_saliency keep their device and pinned buffers per calling thread between calls (a bit
  * plane of the grid, the placements, the scene points; a slab of up to 256 MB once a call took the global route).  They are not
  * freed when the thread ends: a thread that ends while the process goes on calls this first.  Later calls allocate again. */
 int     rs_hip_arrange_release( void );
+
+/* ---- coverage footprints: the coverage term of the simulated-annealing loop without a device call per iteration ---- */
+
+/* rsao_simulated_annealing (arrangement_optimization.cpp:388 ff.) scores one arrangement per iteration, and every placement it can
+ * ever hold is known before the loop: the scene's pose proposals and the placements of the starting arrangement.  The coverage of an
+ * arrangement (:344-373) depends only on WHICH scene-active voxels its non-static placements hit (:1083-1106, :359-367):
+ *   agree = | union of footprint( k ) over its placements |,   score = (float)agree / (float)valid,
+ * footprint( k ) = the distinct cells the transformed level-2 points of placement k fall into that are active in the scene grid.
+ * rs_hip_coverage_footprints computes the footprints of n_placements placements in one device call: placement k puts objects[k] at
+ * poses[16k..]; a static placement (is_static[k], :1095-1096) has the empty footprint and its object may be NULL; so has an empty
+ * cloud.  A point with a NaN or infinite coordinate, or off the grid, has no cell (as in rs_hip_coverage_scores).  The result holds,
+ * per placement, its cells as ascending, duplicate-free int32 indices of the reference's grid (y * x_res * z_res + z * x_res + x),
+ * with the grid's n_cells and valid_cells.  One workgroup per placement, bits in a sub-box in LDS (rs_hip_coverage_lds_budget, as
+ * for rs_hip_coverage_extensions; larger sub-boxes on a slab of global memory), compacted on the device; two blocking read-backs
+ * on the LDS route.  NULL on failure (rs_hip_last_error): RS_HIP_E_ARG conditions are refused before a device is touched.
+ * The buffers are the calling thread's (rs_hip_arrange_release).
+ * A footprints handle lives in host memory.  rs_hip_footprints_scores writes to it (its marks): one thread at a time per handle. */
+typedef struct rs_hip_footprints rs_hip_footprints_t;
+rs_hip_footprints_t* rs_hip_coverage_footprints( rs_hip_coverage_t* c,
+    const rs_hip_cloud_t* const* objects, const float* poses, const int32_t* is_static,
+    int32_t n_placements );
+/* Host only: the same object from arrays (tests, callers that cache footprints).  offsets: n_placements + 1 values from 0 that do not
+ * decrease; placement k's cells are cells[offsets[k] .. offsets[k+1]), strictly ascending, each in [0, n_cells); 0 <= valid_cells <=
+ * n_cells.  Anything else: NULL with RS_HIP_E_ARG's text in rs_hip_last_error (n_cells beyond 2e9: RS_HIP_E_CAPACITY's). */
+rs_hip_footprints_t* rs_hip_footprints_from_arrays( int64_t n_cells, int64_t valid_cells,
+    const int64_t* offsets /* n+1 */, const int32_t* cells, int32_t n_placements );
+void rs_hip_footprints_destroy( rs_hip_footprints_t* f );
+/* Any of the four outputs may be NULL.  total_cells = offsets[n_placements]. */
+int  rs_hip_footprints_info( const rs_hip_footprints_t* f, int32_t* n_placements,
+                             int64_t* n_cells, int64_t* valid_cells, int64_t* total_cells );
+/* offsets: n_placements + 1 values; cells: total_cells values (may be NULL when there are none). */
+int  rs_hip_footprints_arrays( const rs_hip_footprints_t* f, int64_t* offsets, int32_t* cells );
+/* Host only: rsao__compute_scene_coverage_score (:344-373) of arrangement a = members[first[a] .. first[a+1]) (indices into the
+ * footprint set), bit for bit: agree[a] (may be NULL) = the number of distinct cells in its members' footprints, scores[a] =
+ * (float)agree[a] / (float)valid_cells in one fp32 division, 0 when valid_cells is 0 (:367-368).  A member may repeat and counts
+ * once; an empty arrangement scores 0 / valid.  A member outside [0, n_placements) or first[] that decreases: RS_HIP_E_ARG with
+ * nothing written.  The cost of an arrangement is the length of its members' lists: nothing of the grid's size is cleared or read. */
+int  rs_hip_footprints_scores( rs_hip_footprints_t* f, const int32_t* members, const int32_t* first,
+                               int32_t n_arrangements, float* scores, int32_t* agree /* may be NULL */ );
+/* (diagnostics) Placements footprinted on the LDS route and on the slab route since the last reset (static and empty ones count
+ * for the LDS route: they need no sub-box). */
+void rs_hip_coverage_footprint_routes( int64_t* lds, int64_t* slab, int32_t reset );
 
 /* ---- scene saliency: the per-point quality that gates the scene grid (arrangement_optimization.cpp:1109-1160) ---- */
 

@@ -99,6 +99,13 @@ SIGNATURES = {
     "rs_hip_coverage_lds_budget": (C.c_int32, [C.c_int32]),
     "rs_hip_coverage_extension_routes": (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "rs_hip_arrange_release": (C.c_int, []),
+    "rs_hip_coverage_footprints": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "rs_hip_footprints_from_arrays": (C.c_void_p, [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
+    "rs_hip_footprints_destroy": (None, [C.c_void_p]),
+    "rs_hip_footprints_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rs_hip_footprints_arrays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_footprints_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rs_hip_coverage_footprint_routes": (None, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]),
     "rs_hip_voxel_grid_shape": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rs_hip_scene_saliency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
@@ -1079,10 +1086,76 @@ class Coverage:
                                                  sc.ctypes.data, ag.ctypes.data, C.addressof(ba)))
         return sc[:nc], ag[:nc], ba.value
 
+    def footprints(self, placements):
+        """The scene-active cells of every placement in one call (rs_hip_coverage_footprints).  placements: list of (Cloud, pose16,
+        is_static) — a static placement's Cloud may be None.  Returns a Footprints, which scores arrangements of these placements
+        on the host."""
+        for k, p in enumerate(placements):
+            if len(p) != 3 or (not p[2] and p[0] is None) or np.size(p[1]) != 16:
+                raise ValueError(f"footprints: placement {k} is not (Cloud, pose16, is_static)")
+        n = len(placements)
+        objs = (C.c_void_p * max(1, n))(*[None if p[0] is None else p[0].handle for p in placements])
+        poses = _f32(np.array([np.asarray(p[1], np.float32).ravel() for p in placements], np.float32).reshape(-1, 16)) if n else np.zeros((1, 16), np.float32)
+        stat = np.array([int(bool(p[2])) for p in placements] or [0], np.int32)
+        h = load().rs_hip_coverage_footprints(self.handle, C.addressof(objs), poses.ctypes.data, stat.ctypes.data, n)
+        if not h:
+            raise RescanHipError(f"coverage_footprints failed: {load().rs_hip_last_error().decode()}")
+        return Footprints(h)
+
     def __del__(self):
         try:
             if getattr(self, "handle", None):
                 load().rs_hip_coverage_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+class Footprints:
+    """Per placement, the sorted scene-active cells it hits (Coverage.footprints, or Footprints.from_arrays); scores arrangements
+    of these placements as unions, on the host, bit for bit rsao__compute_scene_coverage_score.  One thread at a time per object."""
+
+    def __init__(self, handle):
+        self.handle = handle
+        n, nc, v, t = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        _check(load().rs_hip_footprints_info(self.handle, C.byref(n), C.byref(nc), C.byref(v), C.byref(t)))
+        self.n_placements, self.n_cells, self.valid_cells, self.total_cells = n.value, nc.value, v.value, t.value
+        self.offsets = np.zeros(n.value + 1, np.int64)
+        self._cells = np.zeros(t.value, np.int32)
+        _check(load().rs_hip_footprints_arrays(self.handle, self.offsets.ctypes.data, self._cells.ctypes.data if t.value else None))
+
+    @classmethod
+    def from_arrays(cls, n_cells, valid_cells, offsets, cells):
+        """Host only.  offsets: n + 1 values from 0; placement k's cells = cells[offsets[k]:offsets[k+1]], ascending, no duplicates."""
+        off = np.ascontiguousarray(offsets, np.int64)
+        ce = np.ascontiguousarray(cells, np.int32)
+        if off.ndim != 1 or len(off) < 1 or ce.ndim != 1 or len(ce) < int(off[-1]):
+            raise ValueError("from_arrays: offsets is not n + 1 values, or there are fewer cells than offsets[-1]")
+        h = load().rs_hip_footprints_from_arrays(int(n_cells), int(valid_cells), off.ctypes.data, ce.ctypes.data if len(ce) else None, len(off) - 1)
+        if not h:
+            raise RescanHipError(f"footprints_from_arrays failed: {load().rs_hip_last_error().decode()}")
+        return cls(h)
+
+    def cells(self, k):
+        """Placement k's cells: int32, ascending."""
+        if not 0 <= k < self.n_placements:
+            raise IndexError(k)
+        return self._cells[self.offsets[k]:self.offsets[k + 1]].copy()
+
+    def scores(self, arrangements):
+        """arrangements: list of lists of placement indices.  Returns (scores f32, agree i32)."""
+        first = np.zeros(len(arrangements) + 1, np.int32)
+        first[1:] = np.cumsum([len(a) for a in arrangements])
+        members = np.array([m for a in arrangements for m in a] or [0], np.int32)
+        na = len(arrangements)
+        sc, ag = np.zeros(max(1, na), np.float32), np.zeros(max(1, na), np.int32)
+        _check(load().rs_hip_footprints_scores(self.handle, members.ctypes.data, first.ctypes.data, na, sc.ctypes.data, ag.ctypes.data))
+        return sc[:na], ag[:na]
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                load().rs_hip_footprints_destroy(self.handle)
                 self.handle = None
         except Exception:
             pass
@@ -1101,8 +1174,15 @@ def coverage_extension_routes(reset=False):
     return a.value, b.value
 
 
+def coverage_footprint_routes(reset=False):
+    """(placements footprinted on the LDS route, on the slab route) since the last reset."""
+    a, b = C.c_int64(), C.c_int64()
+    load().rs_hip_coverage_footprint_routes(C.byref(a), C.byref(b), int(bool(reset)))
+    return a.value, b.value
+
+
 def arrange_release():
-    """Frees the buffers Coverage.extensions and scene_saliency keep for the calling thread (a thread that ends calls this first)."""
+    """Frees the buffers Coverage.extensions, Coverage.footprints and scene_saliency keep for the calling thread (a thread that ends calls this first)."""
     _check(load().rs_hip_arrange_release())
 
 

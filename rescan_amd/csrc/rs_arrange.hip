@@ -163,18 +163,154 @@ __global__ __launch_bounds__( ARR_BLOCK ) void k_extend( ExtLaunch L )
   if( tid == 0 ) L.fresh[cand] = s_fresh;
 }
 
+// ---- footprints: the distinct scene-active cells of every placement, as sorted lists ------
+
+// Placement k of rs_hip_coverage_footprints: its cloud (n = 0 for a static placement or an empty cloud), its pose and where its
+// cells start in FpLaunch::cells — the sum of the n before it: a placement hits no more cells than it has points.
+struct FpPlacement { const float4* pos; int n; int pad; long long first; Xform pose; };
+
+struct FpLaunch
+{
+  VoxGrid grid;
+  const uint32_t* scene_bits;
+  const FpPlacement* plc;
+  int lds_bytes;
+  int* count; int* cells;                       // per placement: its number of cells (-1: more cells than points, cannot happen); its cells from plc[k].first
+  int* n_overflow; ArrOverflow* overflow;       // written by the LDS route
+  const ArrSlabJob* jobs; uint32_t* slab;       // read by the global route
+};
+
+#define FP_RUN 16                                // words per thread and trip of the compaction: ARR_BLOCK * FP_RUN words are the whole LDS budget
+#define FP_CHUNK ( ARR_BLOCK * FP_RUN )
+
+// the cell of point i of a placement if the scene grid is active there (:363-364 without an arrangement plane), else -1
+__device__ __forceinline__ int scene_cell( const FpLaunch& L, const FpPlacement& P, int i )
+{
+  const float4 p = P.pos[i];
+  float x, y, z;
+  xform3( P.pose, p.x, p.y, p.z, 1.0f, x, y, z );              // msh_mat4_vec3_mul( pose, p, 1 ), :1101
+  const int c = voxel_of( L.grid, x, y, z );
+  if( c < 0 ) return -1;
+  if( !( L.scene_bits[c >> 5] & ( 1u << ( c & 31 ) ) ) ) return -1;
+  return c;
+}
+
+// One workgroup per placement, k_extend's skeleton: box of the placement's scene-active cells, the sub-box's bits cleared (LDS, or
+// the slab for the placements of L.jobs), one atomicOr per point.  Then the compaction: the sub-box is (y, z, x)-major like the grid's
+// own cell index, so its set bits in order ARE the placement's cells in ascending order.  A trip covers FP_CHUNK words: every thread
+// popcounts a contiguous run of them, an exclusive scan over the workgroup (DPP wave scan, the four waves' totals through LDS) gives
+// its offset, and it writes the global index of each of its set bits from there.  The LDS route needs one trip.
+template <bool GLOBAL>
+__global__ __launch_bounds__( ARR_BLOCK ) void k_footprint( FpLaunch L )
+{
+  __shared__ uint32_t s_bits[GLOBAL ? 1 : ARR_LDS_BYTES / 4];
+  __shared__ int s_box[6];
+  __shared__ uint32_t s_wave[ARR_BLOCK / 64];
+  const int tid = threadIdx.x;
+  const int k = GLOBAL ? L.jobs[blockIdx.x].cand : (int)blockIdx.x;
+  const FpPlacement P = L.plc[k];                              // (uniform: scalar registers)
+  const int xz = L.grid.x_res * L.grid.z_res, xr = L.grid.x_res;
+  if( tid < 3 ) { s_box[tid] = INT_MAX; s_box[3 + tid] = INT_MIN; }
+  __syncthreads();
+  int lo[3] = { INT_MAX, INT_MAX, INT_MAX }, hi[3] = { INT_MIN, INT_MIN, INT_MIN };
+  for( int i = tid; i < P.n; i += ARR_BLOCK )
+  {
+    const int c = scene_cell( L, P, i );
+    if( c < 0 ) continue;
+    const int cy = c / xz, r = c - cy * xz, cz = r / xr, cx = r - cz * xr;          // :108 backwards
+    lo[0] = min( lo[0], cx ); hi[0] = max( hi[0], cx ); lo[1] = min( lo[1], cy ); hi[1] = max( hi[1], cy ); lo[2] = min( lo[2], cz ); hi[2] = max( hi[2], cz );
+  }
+  for( int a = 0; a < 3; ++a ) { lo[a] = wave_min( lo[a] ); hi[a] = wave_max( hi[a] ); }
+  if( ( tid & 63 ) == 0 ) for( int a = 0; a < 3; ++a ) { atomicMin( &s_box[a], lo[a] ); atomicMax( &s_box[3 + a], hi[a] ); }
+  __syncthreads();
+  const int x0 = s_box[0], y0 = s_box[1], z0 = s_box[2];
+  if( s_box[3] < x0 ) { if( tid == 0 ) L.count[k] = 0; return; }                     // no scene-active cell (uniform)
+  const int sx = s_box[3] - x0 + 1, sy = s_box[4] - y0 + 1, sz = s_box[5] - z0 + 1;
+  const unsigned long long words = ( (unsigned long long)sx * sy * sz + 31ull ) >> 5;   // (at most the grid's own plane: below 2^26)
+  if( !GLOBAL && words * 4ull > (unsigned long long)L.lds_bytes )
+  {
+    if( tid == 0 ) { const int slot = atomicAdd( L.n_overflow, 1 ); L.overflow[slot] = ArrOverflow{ k, 0, words }; L.count[k] = 0; }
+    return;
+  }
+  if( GLOBAL && words != L.jobs[blockIdx.x].words ) { if( tid == 0 ) L.count[k] = -2; return; }     // (the same walk over the same plane: cannot differ)
+  uint32_t* bits = GLOBAL ? L.slab + L.jobs[blockIdx.x].off : s_bits;
+  for( unsigned long long w = tid; w < words; w += ARR_BLOCK ) bits[w] = 0u;
+  __syncthreads();
+  for( int i = tid; i < P.n; i += ARR_BLOCK )
+  {
+    const int c = scene_cell( L, P, i );
+    if( c < 0 ) continue;
+    const int cy = c / xz, r = c - cy * xz, cz = r / xr, cx = r - cz * xr;
+    const unsigned long long b = ( (unsigned long long)( cy - y0 ) * sz + ( cz - z0 ) ) * sx + ( cx - x0 );
+    atomicOr( bits + ( b >> 5 ), 1u << ( b & 31ull ) );                              // several points in one cell: one bit
+  }
+  __syncthreads();
+  // (the slab's words were written by atomics of other waves: read them where the atomics were made, past this CU's vector cache)
+  auto word = [&]( unsigned long long w ) -> uint32_t { return GLOBAL ? __hip_atomic_load( bits + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT ) : bits[w]; };
+  const uint32_t sxz = (uint32_t)sx * (uint32_t)sz;
+  int* out = L.cells + P.first;
+  uint32_t done = 0;                                                                  // cells of the trips before this one
+  for( unsigned long long w_base = 0; w_base < words; w_base += FP_CHUNK )            // (uniform)
+  {
+    const uint32_t span = (uint32_t)min( words - w_base, (unsigned long long)FP_CHUNK );
+    const uint32_t per = ( span + ARR_BLOCK - 1 ) / ARR_BLOCK;                        // <= FP_RUN
+    const uint32_t w0 = min( (uint32_t)tid * per, span ), w1 = min( w0 + per, span );
+    uint32_t mine = 0;
+    for( uint32_t w = w0; w < w1; ++w ) mine += __popc( word( w_base + w ) );
+    const uint32_t incl = wave_scan( mine, tid & 63 );
+    if( ( tid & 63 ) == 63 ) s_wave[tid >> 6] = incl;
+    __syncthreads();
+    uint32_t o = done + incl - mine, total = 0;
+    for( int v = 0; v < ARR_BLOCK / 64; ++v ) { const uint32_t t = s_wave[v]; if( v < ( tid >> 6 ) ) o += t; total += t; }
+    for( uint32_t w = w0; w < w1; ++w )
+    {
+      uint32_t v = word( w_base + w );
+      while( v )
+      {
+        const uint32_t b = (uint32_t)( w_base + w ) * 32u + (uint32_t)( __ffs( v ) - 1 );
+        v &= v - 1u;
+        const uint32_t dy = b / sxz, r = b - dy * sxz, dz = r / (uint32_t)sx, dx = r - dz * (uint32_t)sx;
+        if( o < (uint32_t)P.n ) out[o] = ( y0 + (int)dy ) * xz + ( z0 + (int)dz ) * xr + x0 + (int)dx;     // (never past the placement's own region)
+        ++o;
+      }
+    }
+    done += total;
+    __syncthreads();                                                                  // (s_wave is written again by the next trip)
+  }
+  if( tid == 0 ) L.count[k] = done <= (uint32_t)P.n ? (int)done : -1;
+}
+
+// The tight CSR: placement k's cells copied from its region of `cells` to tight[ sum of the counts before k ...).  Every workgroup
+// sums the counts before its own (a few hundred placements: one or two trips); a negative count (an overflowed placement's 0 is
+// not one) copies nothing.
+__global__ __launch_bounds__( ARR_BLOCK ) void k_footprint_pack( const FpPlacement* plc, const int* count, const int* cells, int* tight )
+{
+  __shared__ long long s_before[ARR_BLOCK / 64];
+  const int k = blockIdx.x, tid = threadIdx.x;
+  long long before = 0;
+  for( int j = tid; j < k; j += ARR_BLOCK ) before += max( count[j], 0 );
+  for( int o = 32; o; o >>= 1 ) before += __shfl_xor( before, o, 64 );
+  if( ( tid & 63 ) == 0 ) s_before[tid >> 6] = before;
+  __syncthreads();
+  before = 0;
+  for( int v = 0; v < ARR_BLOCK / 64; ++v ) before += s_before[v];
+  const int n = min( count[k], plc[k].n );
+  const int* src = cells + plc[k].first;
+  for( int i = tid; i < n; i += ARR_BLOCK ) tight[before + i] = src[i];
+}
+
 // ------------------------------------------------------------------------------------------
 
-// The calling thread's buffers, grown on demand and kept between calls (a base plane, the placements, and a slab of up to
-// ARR_SLAB_BYTES once a call took the global route).  No destructor frees them (rs_host.h: Buf); a thread that ends while the
-// process goes on gives them back with rs_hip_arrange_release().
+// The calling thread's buffers, grown on demand and kept between calls (a base plane, the placements, the footprints' cells, and a
+// slab of up to ARR_SLAB_BYTES once a call took the global route).  No destructor frees them (rs_host.h: Buf); a thread that ends
+// while the process goes on gives them back with rs_hip_arrange_release().
 struct ArrWorkspace
 {
-  Buf props, bits, pos, cls, quality, base, plc, out, over, jobs, slab, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true };
+  Buf props, bits, pos, cls, quality, base, plc, out, over, jobs, slab, fp_cells, fp_tight, h_in{ nullptr, 0, true }, h_out{ nullptr, 0, true };
   hipError_t release()
   {
     hipError_t first = hipSuccess;
-    for( Buf* b : { &props, &bits, &pos, &cls, &quality, &base, &plc, &out, &over, &jobs, &slab, &h_in, &h_out } )
+    for( Buf* b : { &props, &bits, &pos, &cls, &quality, &base, &plc, &out, &over, &jobs, &slab, &fp_cells, &fp_tight, &h_in, &h_out } )
     {
       const hipError_t e = b->release();
       if( first == hipSuccess ) first = e;
@@ -185,9 +321,142 @@ struct ArrWorkspace
 thread_local ArrWorkspace g_arr_ws;
 // process-wide, read and written by any calling thread
 std::atomic<int> g_arr_lds_bytes{ ARR_LDS_BYTES };
-std::atomic<int64_t> g_arr_lds_route{ 0 }, g_arr_slab_route{ 0 };
+std::atomic<int64_t> g_arr_lds_route{ 0 }, g_arr_slab_route{ 0 }, g_fp_lds_route{ 0 }, g_fp_slab_route{ 0 };
+
+// The device part of rs_hip_coverage_footprints, arguments checked by its caller: offsets (n + 1) and the cells of every placement.
+// Stream order of the LDS route: upload, k_footprint<false>, k_footprint_pack, read-back 1 (overflow count and counts), read-back
+// 2 (the tight cells, whose number read-back 1 told).  Overflowed placements count 0 in the first launch; with any of them the
+// overflow list is read, k_footprint<true> fills their regions, and the pack and the two read-backs are made again.
+int footprints_device( rs_hip_coverage_t* c, const rs_hip_cloud_t* const* objects, const float* poses, const int32_t* is_static, int32_t n,
+                       std::vector<int64_t>& offsets, std::vector<int32_t>& cells )
+{
+  offsets.assign( (size_t)n + 1, 0 ); cells.clear();
+  hipStream_t st = nullptr;
+  int rc = api_ready( &st ); if( rc ) return rc;
+  if( n == 0 ) return RS_HIP_OK;
+  ArrWorkspace& W = g_arr_ws;
+  std::vector<FpPlacement> plc( (size_t)n );
+  long long total = 0;
+  for( int32_t k = 0; k < n; ++k )
+  {
+    FpPlacement p{}; p.first = total;
+    if( !is_static[k] )                                          // :1095-1096
+    {
+      const GridView* v = api_cloud_view( objects[k] );
+      if( v->n > 0 ) { p.pos = v->pos; p.n = v->n; }
+    }
+    std::memcpy( p.pose.m, poses + 16 * (size_t)k, 64 );
+    plc[k] = p; total += p.n;
+  }
+  // device words of a call: [0] placements on the overflow list, [1] unused, [2 ..) cells per placement
+  const size_t out_ints = 2 + (size_t)n, cell_bytes = std::max<size_t>( 1, (size_t)total ) * 4;
+  RS_TRY_DRAIN( st, W.out.ensure( out_ints * 4 ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.over.ensure( (size_t)n * sizeof(ArrOverflow) ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.plc.ensure( (size_t)n * sizeof(FpPlacement) ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.fp_cells.ensure( cell_bytes ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.fp_tight.ensure( cell_bytes ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.h_in.ensure( (size_t)n * sizeof(FpPlacement) ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, W.h_out.ensure( out_ints * 4 + 8 + (size_t)n * sizeof(ArrOverflow) ), "coverage_footprints: buffers" );
+  RS_TRY_DRAIN( st, hipMemsetAsync( W.out.p, 0, 8, st ), "coverage_footprints: clear" );
+  std::memcpy( W.h_in.p, plc.data(), (size_t)n * sizeof(FpPlacement) );
+  RS_TRY_DRAIN( st, hipMemcpyAsync( W.plc.p, W.h_in.p, (size_t)n * sizeof(FpPlacement), hipMemcpyHostToDevice, st ), "coverage_footprints: upload" );
+  int* d_out = (int*)W.out.p;
+  FpLaunch L{};
+  L.grid = c->grid; L.scene_bits = c->d_bits; L.plc = (const FpPlacement*)W.plc.p; L.lds_bytes = g_arr_lds_bytes.load();
+  L.count = d_out + 2; L.cells = (int*)W.fp_cells.p; L.n_overflow = d_out; L.overflow = (ArrOverflow*)W.over.p;
+  int* h_out = (int*)W.h_out.p;
+  // the pack, read-back 1 and, once every count is final, read-back 2
+  auto pack_and_read = [&]( bool final ) -> int
+  {
+    {
+      ProfSpan span( "footprints" );
+      hipLaunchKernelGGL( k_footprint_pack, dim3( (unsigned)n ), dim3( ARR_BLOCK ), 0, st, L.plc, (const int*)L.count, (const int*)L.cells, (int*)W.fp_tight.p );
+    }
+    RS_TRY_DRAIN( st, hipGetLastError(), "coverage_footprints: launch" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( h_out, d_out, out_ints * 4, hipMemcpyDeviceToHost, st ), "coverage_footprints: download" );
+    RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_footprints" );
+    if( !final && h_out[0] != 0 ) return RS_HIP_OK;              // (the slab route comes first)
+    for( int32_t k = 0; k < n; ++k )
+    {
+      const int cnt = h_out[2 + k];
+      if( cnt == -2 ) return fail( RS_HIP_E_RUNTIME, "coverage_footprints: a sub-box changed between the two routes" );
+      if( cnt < 0 || cnt > plc[k].n ) return fail( RS_HIP_E_RUNTIME, "coverage_footprints: a placement with more cells than points" );
+      offsets[(size_t)k + 1] = offsets[k] + cnt;
+    }
+    cells.resize( (size_t)offsets[n] );
+    if( !cells.empty() )
+    {
+      RS_TRY_DRAIN( st, hipMemcpyAsync( cells.data(), W.fp_tight.p, cells.size() * 4, hipMemcpyDeviceToHost, st ), "coverage_footprints: download" );
+      RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_footprints" );
+    }
+    return RS_HIP_OK;
+  };
+  {
+    ProfSpan span( "footprints" );
+    hipLaunchKernelGGL( k_footprint<false>, dim3( (unsigned)n ), dim3( ARR_BLOCK ), 0, st, L );
+  }
+  rc = pack_and_read( false ); if( rc ) return rc;
+  const int n_over = h_out[0];
+  if( n_over < 0 || n_over > n ) return fail( RS_HIP_E_RUNTIME, "coverage_footprints: overflow list out of range" );
+  if( n_over > 0 )
+  {
+    ArrOverflow* ho = (ArrOverflow*)( h_out + out_ints + ( out_ints & 1 ) );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( ho, W.over.p, (size_t)n_over * sizeof(ArrOverflow), hipMemcpyDeviceToHost, st ), "coverage_footprints: download" );
+    RS_TRY_DRAIN( st, hipStreamSynchronize( st ), "coverage_footprints" );
+    std::sort( ho, ho + n_over, []( const ArrOverflow& a, const ArrOverflow& b ) { return a.cand < b.cand; } );       // (the list's order is the workgroups')
+    std::vector<ArrSlabJob> jobs( n_over );
+    std::vector<std::pair<int, int>> chunks;                       // launches of at most ARR_SLAB_BYTES of sub-boxes
+    size_t slab_words = 0;
+    for( int i = 0; i < n_over; )
+    {
+      size_t used = 0; int j = i;
+      while( j < n_over && ( j == i || ( used + ho[j].words ) * 4 <= ARR_SLAB_BYTES ) )
+      {
+        if( ho[j].cand < 0 || ho[j].cand >= n || ho[j].words > (unsigned long long)c->n_words ) return fail( RS_HIP_E_RUNTIME, "coverage_footprints: overflow entry out of range" );
+        jobs[j] = ArrSlabJob{ ho[j].cand, 0, used, ho[j].words }; used += ho[j].words; ++j;
+      }
+      chunks.emplace_back( i, j ); slab_words = std::max( slab_words, used ); i = j;
+    }
+    RS_TRY_DRAIN( st, W.slab.ensure( slab_words * 4 ), "coverage_footprints: scratch slab" );
+    RS_TRY_DRAIN( st, W.jobs.ensure( jobs.size() * sizeof(ArrSlabJob) ), "coverage_footprints: buffers" );
+    RS_TRY_DRAIN( st, hipMemcpyAsync( W.jobs.p, jobs.data(), jobs.size() * sizeof(ArrSlabJob), hipMemcpyHostToDevice, st ), "coverage_footprints: upload" );
+    L.slab = (uint32_t*)W.slab.p;
+    {
+      ProfSpan span( "footprints" );
+      for( const auto& ch : chunks )
+      {
+        L.jobs = (const ArrSlabJob*)W.jobs.p + ch.first;
+        hipLaunchKernelGGL( k_footprint<true>, dim3( (unsigned)( ch.second - ch.first ) ), dim3( ARR_BLOCK ), 0, st, L );
+      }
+    }
+    rc = pack_and_read( true ); if( rc ) return rc;                // (its first synchronisation also keeps `jobs` alive until the upload is done)
+  }
+  g_fp_lds_route += n - n_over; g_fp_slab_route += n_over;
+  return RS_HIP_OK;
+}
 
 } // namespace
+
+// rs_hip_coverage_footprints' result, or the same from arrays: host memory only.  `dense` holds every cell as its rank among the
+// set's distinct cells, so that a union is counted on a stamp array as long as that set, not as the grid: rs_hip_footprints_scores
+// marks a cell with the arrangement's epoch and counts the first mark; nothing is cleared between arrangements.
+struct rs_hip_footprints
+{
+  int64_t n_cells = 0, valid = 0;
+  std::vector<int64_t> offsets{ 0 };
+  std::vector<int32_t> cells, dense;
+  std::vector<uint32_t> stamp;
+  uint32_t epoch = 0;
+  void index()
+  {
+    std::vector<int32_t> u( cells );
+    std::sort( u.begin(), u.end() );
+    u.erase( std::unique( u.begin(), u.end() ), u.end() );
+    dense.resize( cells.size() );
+    for( size_t i = 0; i < cells.size(); ++i ) dense[i] = (int32_t)( std::lower_bound( u.begin(), u.end(), cells[i] ) - u.begin() );
+    stamp.assign( u.size(), 0u ); epoch = 0;
+  }
+};
 
 extern "C" {
 
@@ -415,7 +684,7 @@ int rs_hip_arrange_release( void )
 {
   ArrWorkspace& W = g_arr_ws;
   bool any = false;
-  for( const Buf* b : { &W.props, &W.bits, &W.pos, &W.cls, &W.quality, &W.base, &W.plc, &W.out, &W.over, &W.jobs, &W.slab, &W.h_in, &W.h_out } ) any = any || b->p;
+  for( const Buf* b : { &W.props, &W.bits, &W.pos, &W.cls, &W.quality, &W.base, &W.plc, &W.out, &W.over, &W.jobs, &W.slab, &W.fp_cells, &W.fp_tight, &W.h_in, &W.h_out } ) any = any || b->p;
   if( !any ) return RS_HIP_OK;                                   // (nothing held: no device is touched)
   hipStream_t st = nullptr;
   int rc = api_ready( &st ); if( rc ) return rc;
@@ -431,6 +700,114 @@ void rs_hip_coverage_extension_routes( int64_t* lds, int64_t* slab, int32_t rese
   if( slab ) *slab = reset ? g_arr_slab_route.exchange( 0 ) : g_arr_slab_route.load();
   if( reset && !lds ) g_arr_lds_route = 0;
   if( reset && !slab ) g_arr_slab_route = 0;
+}
+
+rs_hip_footprints_t* rs_hip_coverage_footprints( rs_hip_coverage_t* c, const rs_hip_cloud_t* const* objects, const float* poses,
+                                                 const int32_t* is_static, int32_t n_placements )
+{
+  if( !c || n_placements < 0 || ( n_placements > 0 && ( !objects || !poses || !is_static ) ) )
+  { fail( RS_HIP_E_ARG, "coverage_footprints: bad arguments" ); return nullptr; }
+  for( int32_t k = 0; k < n_placements; ++k )
+    if( !is_static[k] && !objects[k] )
+    {
+      char msg[128]; snprintf( msg, sizeof(msg), "coverage_footprints: placement %d has no object cloud", k );
+      fail( RS_HIP_E_ARG, msg ); return nullptr;
+    }
+  hipStream_t st = nullptr;
+  if( api_ready( &st ) ) return nullptr;                         // (no device: its error text stands; the handle is not read before)
+  rs_hip_footprints_t* f = new rs_hip_footprints_t();
+  f->n_cells = c->grid.n_cells; f->valid = c->valid;
+  if( footprints_device( c, objects, poses, is_static, n_placements, f->offsets, f->cells ) ) { delete f; return nullptr; }
+  f->index();
+  return f;
+}
+
+rs_hip_footprints_t* rs_hip_footprints_from_arrays( int64_t n_cells, int64_t valid_cells, const int64_t* offsets, const int32_t* cells, int32_t n_placements )
+{
+  if( n_cells < 0 || valid_cells < 0 || valid_cells > n_cells || n_placements < 0 || !offsets || offsets[0] != 0 )
+  { fail( RS_HIP_E_ARG, "footprints_from_arrays: bad arguments" ); return nullptr; }
+  if( n_cells > 2000000000ll ) { fail( RS_HIP_E_CAPACITY, "footprints_from_arrays: the cells do not fit the reference's int32 cell index" ); return nullptr; }
+  for( int32_t k = 0; k < n_placements; ++k )
+    if( offsets[k + 1] < offsets[k] )
+    {
+      char msg[128]; snprintf( msg, sizeof(msg), "footprints_from_arrays: the offsets decrease at placement %d", k );
+      fail( RS_HIP_E_ARG, msg ); return nullptr;
+    }
+  if( offsets[n_placements] > 0 && !cells ) { fail( RS_HIP_E_ARG, "footprints_from_arrays: bad arguments" ); return nullptr; }
+  for( int32_t k = 0; k < n_placements; ++k )
+    for( int64_t i = offsets[k]; i < offsets[k + 1]; ++i )
+      if( cells[i] < 0 || cells[i] >= n_cells || ( i > offsets[k] && cells[i] <= cells[i - 1] ) )
+      {
+        char msg[160]; snprintf( msg, sizeof(msg), "footprints_from_arrays: placement %d: cell %d at %lld is outside the grid, or not above the cell before it", k, cells[i], (long long)i );
+        fail( RS_HIP_E_ARG, msg ); return nullptr;
+      }
+  rs_hip_footprints_t* f = new rs_hip_footprints_t();
+  f->n_cells = n_cells; f->valid = valid_cells;
+  f->offsets.assign( offsets, offsets + n_placements + 1 );
+  if( offsets[n_placements] > 0 ) f->cells.assign( cells, cells + offsets[n_placements] );
+  f->index();
+  return f;
+}
+
+void rs_hip_footprints_destroy( rs_hip_footprints_t* f ) { delete f; }
+
+int rs_hip_footprints_info( const rs_hip_footprints_t* f, int32_t* n_placements, int64_t* n_cells, int64_t* valid_cells, int64_t* total_cells )
+{
+  if( !f ) return fail( RS_HIP_E_ARG, "footprints_info: null handle" );
+  if( n_placements ) *n_placements = (int32_t)( f->offsets.size() - 1 );
+  if( n_cells ) *n_cells = f->n_cells;
+  if( valid_cells ) *valid_cells = f->valid;
+  if( total_cells ) *total_cells = f->offsets.back();
+  return RS_HIP_OK;
+}
+
+int rs_hip_footprints_arrays( const rs_hip_footprints_t* f, int64_t* offsets, int32_t* cells )
+{
+  if( !f || !offsets || ( !cells && !f->cells.empty() ) ) return fail( RS_HIP_E_ARG, "footprints_arrays: bad arguments" );
+  std::memcpy( offsets, f->offsets.data(), f->offsets.size() * sizeof(int64_t) );
+  if( !f->cells.empty() ) std::memcpy( cells, f->cells.data(), f->cells.size() * sizeof(int32_t) );
+  return RS_HIP_OK;
+}
+
+int rs_hip_footprints_scores( rs_hip_footprints_t* f, const int32_t* members, const int32_t* first, int32_t n_arrangements, float* scores, int32_t* agree )
+{
+  if( !f || n_arrangements < 0 || ( n_arrangements > 0 && ( !first || !scores ) ) ) return fail( RS_HIP_E_ARG, "footprints_scores: bad arguments" );
+  if( n_arrangements == 0 ) return RS_HIP_OK;
+  const int32_t n = (int32_t)( f->offsets.size() - 1 );
+  if( first[0] < 0 || ( first[n_arrangements] > first[0] && !members ) ) return fail( RS_HIP_E_ARG, "footprints_scores: bad arguments" );
+  for( int32_t a = 0; a < n_arrangements; ++a )
+  {
+    if( first[a + 1] < first[a] ) return fail( RS_HIP_E_ARG, "footprints_scores: the arrangements' first members decrease" );
+    for( int32_t i = first[a]; i < first[a + 1]; ++i )
+      if( members[i] < 0 || members[i] >= n )
+      {
+        char msg[128]; snprintf( msg, sizeof(msg), "footprints_scores: arrangement %d names member %d outside [0, %d)", a, members[i], n );
+        return fail( RS_HIP_E_ARG, msg );
+      }
+  }
+  const int32_t* dense = f->dense.data(); const int64_t* off = f->offsets.data(); uint32_t* stamp = f->stamp.data();
+  for( int32_t a = 0; a < n_arrangements; ++a )
+  {
+    if( ++f->epoch == 0u ) { std::fill( f->stamp.begin(), f->stamp.end(), 0u ); f->epoch = 1u; }     // (once in 2^32 arrangements)
+    const uint32_t e = f->epoch;
+    int32_t cnt = 0;
+    for( int32_t i = first[a]; i < first[a + 1]; ++i )
+      for( int64_t j = off[members[i]], end = off[members[i] + 1]; j < end; ++j )
+        if( stamp[dense[j]] != e ) { stamp[dense[j]] = e; ++cnt; }                     // a cell of several members, or of a repeated one, counts once
+    float s = (float)cnt / (float)f->valid;                        // :366
+    if( f->valid == 0 ) s = 0.0f;                                  // :367
+    scores[a] = s;
+    if( agree ) agree[a] = cnt;
+  }
+  return RS_HIP_OK;
+}
+
+void rs_hip_coverage_footprint_routes( int64_t* lds, int64_t* slab, int32_t reset )
+{
+  if( lds ) *lds = reset ? g_fp_lds_route.exchange( 0 ) : g_fp_lds_route.load();
+  if( slab ) *slab = reset ? g_fp_slab_route.exchange( 0 ) : g_fp_slab_route.load();
+  if( reset && !lds ) g_fp_lds_route = 0;
+  if( reset && !slab ) g_fp_slab_route = 0;
 }
 
 } // extern "C"

@@ -1060,6 +1060,38 @@ int rsd_coverage_extensions( void* coverage, const rsd_vec3_t* const* base_pos, 
   return rc;
 }
 
+void* rsd_coverage_footprints( void* coverage, const rsd_vec3_t* const* obj_pos, const int32_t* obj_n, const rsd_mat4_t* poses,
+                               const int32_t* is_static, int32_t n_plc )
+{
+  if( !coverage || n_plc < 0 || ( n_plc > 0 && ( !obj_pos || !obj_n || !poses || !is_static ) ) )
+  { fprintf( stderr, "rescan_dropin: coverage_footprints: null arrays or a negative count\n" ); return nullptr; }
+  for( int i = 0; i < n_plc; ++i )
+    if( !is_static[i] && ( !obj_pos[i] || obj_n[i] < 0 ) ) { fprintf( stderr, "rescan_dropin: coverage_footprints: placement %d has no cloud\n", i ); return nullptr; }
+  // every cloud is HELD for the call (see rsd_arrangement_to_labels)
+  std::vector<CloudRef> held( (size_t)n_plc );
+  std::vector<const rs_hip_cloud_t*> objs( held.size(), nullptr );
+  for( int i = 0; i < n_plc; ++i )
+  {
+    if( is_static[i] ) continue;
+    held[i] = cached_cloud( obj_pos[i], nullptr, obj_n[i], -1.0f );
+    if( !held[i] ) return nullptr;
+    objs[i] = held[i].get();
+  }
+  rs_hip_footprints_t* f = rs_hip_coverage_footprints( (rs_hip_coverage_t*)coverage, objs.data(), (const float*)poses, is_static, n_plc );
+  if( !f ) complain( "coverage_footprints" );
+  return f;
+}
+
+float rsd_footprints_score( void* footprints, const int32_t* members, int32_t n_members )
+{
+  const int32_t first[2] = { 0, n_members };
+  float score = 0.0f;
+  if( n_members < 0 || rs_hip_footprints_scores( (rs_hip_footprints_t*)footprints, members, first, 1, &score, nullptr ) ) { complain( "footprints_score" ); return -1.0f; }
+  return score;
+}
+
+void rsd_footprints_destroy( void* footprints ) { rs_hip_footprints_destroy( (rs_hip_footprints_t*)footprints ); }
+
 int rsd_scene_saliency( const rsd_vec3_t* bbox_min, const rsd_vec3_t* bbox_max, float voxel_size,
                         const rsd_vec3_t* const* obj_pos, const int32_t* obj_n, int32_t n_objects,
                         const int32_t* prop_object, const rsd_mat4_t* prop_poses, const int32_t* prop_static, int32_t n_props,
