@@ -50,7 +50,7 @@ def rounds_of(g, prefix):
 
 
 def test_fixtures_are_small_and_hold_the_cases():
-    for name in ("room", "quirks", "gather"):
+    for name in ("room", "quirks", "gather", "hostile"):
         assert os.path.getsize(os.path.join(ROOT, "tests", "golden", f"planes_{name}.npz")) < 757075
     g = load_golden("planes_room.npz")
     assert 8000 <= len(g["pos"]) <= 20000 and int(g["n_rounds"]) - 1 >= 3 and int(g["n_floors"]) == 1
@@ -63,6 +63,10 @@ def test_fixtures_are_small_and_hold_the_cases():
     o = t["checked_offsets"]
     assert o[2] == o[3] and t["model_valid"].tolist() == [1, 1, 0, 1]
     assert (t["instance_before"] >= 1024).any() and (t["class_before"] != 0).any() and ((t["class_before"] != t["class_after"]) | (t["instance_before"] != t["instance_after"])).any()
+    h = load_golden("planes_hostile.npz")                # tests/test_hard_planes_cpu.py compares every array of it
+    assert len(h["vote_cases"]) == 8 and all(h[f"votes_{k}_counts_all"].shape == (64,) and h[f"votes_{k}_removed"].shape[0] == 8 for k in h["vote_cases"])
+    assert not np.isfinite(h["votes_special_pos"]).all() and not np.isfinite(h["room_nor"]).all() and int(h["room_n_rounds"]) >= 3 and int(h["tie_n_rounds"]) >= 3
+    assert all(f"gather_{k}_{a}" in h for k in ("dot_band", "quad_edges", "labels") for a in ("plain_index", "checked_index", "class_after", "instance_after"))
 
 
 @pytest.mark.parametrize("name,prefix", CASES)

@@ -7,6 +7,7 @@
 //                rs_pointcloud_transform, the two loops that set the instance ids to 0 and 1, rs_pointcloud_merge, and the
 //                overwrite of the instance ids with the placement's uidx.  The clouds are assembled with rs_pointcloud_init /
 //                rs_pointcloud__allocate_level.
+//   fx_transform rs_pointcloud_transform of a level 0 assembled from positions and normals, for the hostile transforms.
 //   fx_merge_ids rs_pointcloud_merge of two clouds whose instance ids carry the element's index in "A then B": the ids of the
 //                result are the shuffle's permutation.
 #define MSH_STD_IMPLEMENTATION
@@ -119,6 +120,20 @@ void* fx_augment( const fx_arrays* scan, int64_t n_scan, const fx_arrays* model,
   rs_pointcloud_free( cur_shape, 1 );
   rs_pointcloud_free( input_scan, 1 );
   return merged_shape;
+}
+
+// rs_pointcloud_transform alone (no level build): pos and nor (n points each) are rewritten in place
+void fx_transform( float* pos, float* nor, int64_t n, const float* xform )
+{
+  rs_pointcloud_t* pc = rs_pointcloud_init( 1 );
+  rs_pointcloud__allocate_level( pc, 0, (int32_t)n );
+  memcpy( pc->positions[0], pos, n * 12 );
+  memcpy( pc->normals[0], nor, n * 12 );
+  msh_mat4_t m; memcpy( m.data, xform, 64 );
+  rs_pointcloud_transform( pc, m, 0 );
+  memcpy( pos, pc->positions[0], n * 12 );
+  memcpy( nor, pc->normals[0], n * 12 );
+  rs_pointcloud_free( pc, 1 );
 }
 
 void fx_get( void* h, fx_arrays* out ) { fx_read( (rs_pointcloud_t*)h, 0, out ); }

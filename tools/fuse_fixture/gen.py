@@ -15,6 +15,9 @@ Fixtures (tests/test_fuse_cpu.py, tests/test_gpu_fuse.py compare every array bit
               chair model level 0, the chair's pose perturbed.  The scan's and the model's seven arrays, the extracted arrays, xform
               after the ICP, the ICP's error, the seven merged arrays, the sizes of the merged cloud's five levels.
   fuse_wall   a static placement (no ICP) of one wall of a sparser scan, and an id that no scan point carries: nothing extracted.
+  fuse_hostile  rs_pointcloud_transform of the points of tests/hard_fuse.py (+-0, subnormal, Inf, NaN, FLT_MAX coordinates; and a
+              finite set) under each of its transforms: identity, a translation of 1e4, a rotation, scales of 1e-20 and 1e20, a
+              matrix of -0.0, a translation of Inf and NaN.
 
     python tools/fuse_fixture/gen.py --time
 
@@ -70,6 +73,7 @@ def load(lib):
     L.fx_get.argtypes = [C.c_void_p, C.c_void_p]
     L.fx_free.argtypes = [C.c_void_p]
     L.fx_merge_ids.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.fx_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     return L
 
 
@@ -186,6 +190,25 @@ def write_wall(L, out_dir):
     print(f"wall: {len(scan['pos'])} scan points, {n_ext} extracted, {len(model['pos'])} model points, levels {r['levels'].tolist()}, {size} bytes -> {path}")
 
 
+def write_hostile(L, out_dir):
+    """fuse_hostile: rs_pointcloud_transform of the points of tests/hard_fuse.py under each of its transforms (inputs included)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_fuse as H
+    out = {}
+    for tag, pts in (("", H.points()), ("finite_", H.points(finite=True))):
+        out[tag + "a_pos"], out[tag + "a_nor"] = pts["a_pos"], pts["a_nor"]
+        for name, x in H.transforms().items():
+            pos, nor = pts["a_pos"].copy(), pts["a_nor"].copy()
+            L.fx_transform(pos.ctypes.data, nor.ctypes.data, len(pos), x.ctypes.data)
+            out[f"{tag}{name}_xform"], out[f"{tag}{name}_pos"], out[f"{tag}{name}_nor"] = x, pos, nor
+    out["names"] = np.array(list(H.transforms()))
+    z = out["negzero_nor"][(out["a_nor"] == 0).all(axis=1)]
+    assert len(z) and not np.signbit(z).any(), "the zero normals under the -0 matrix are not +0"
+    assert np.isnan(out["inf_nan_nor"]).all() and np.isinf(out["huge_pos"]).any() and np.isnan(out["huge_pos"]).any()
+    path, size = save(out_dir, "hostile", out)
+    print(f"hostile: {len(out['a_pos'])} points x {len(out['names'])} transforms, twice, {size} bytes -> {path}")
+
+
 def time_reference(L):
     import fuse_timing as T
     rng = np.random.default_rng(405)
@@ -204,6 +227,7 @@ def main():
     ap.add_argument("--time", action="store_true", help="only print the reference's CPU times for the placements of tools/fuse_timing.py")
     ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
+    ap.add_argument("--only", default="", help="write this fixture alone (perm, chair, wall, hostile)")
     a = ap.parse_args()
     here = os.path.dirname(os.path.abspath(__file__))
     with tempfile.TemporaryDirectory() as tmp:
@@ -213,9 +237,9 @@ def main():
         L = load(lib)
         if a.time:
             return time_reference(L)
-        write_perm(L, a.out)
-        write_chair(L, a.out)
-        write_wall(L, a.out)
+        for name, write in (("perm", write_perm), ("chair", write_chair), ("wall", write_wall), ("hostile", write_hostile)):
+            if a.only in ("", name):
+                write(L, a.out)
 
 
 if __name__ == "__main__":

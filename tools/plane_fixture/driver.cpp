@@ -127,6 +127,19 @@ void fx_score( float* pos, int64_t n, double* weights, const int32_t* idx, int32
   }
 }
 
+// evaluate_plane_model for hypotheses given as centre and normal (the hostile fixture's planes come from no triple)
+void fx_votes( float* pos, int64_t n, double* weights, const float* center, const float* normal, int32_t n_hyp, float dist_threshold,
+               int32_t* counts )
+{
+  for( int32_t i = 0; i < n_hyp; ++i )
+  {
+    rspf_plane_model_t model; memset( &model, 0, sizeof(model) );
+    memcpy( &model.plane.center, center + 3 * i, 12 ); memcpy( &model.plane.normal, normal + 3 * i, 12 );
+    evaluate_plane_model( &model, weights, (msh_vec3_t*)pos, (size_t)n, dist_threshold );
+    counts[i] = (int32_t)model.n_inliers;
+  }
+}
+
 void fx_remove( float* pos, int64_t n, double* weights, const float* center, const float* normal, float dist_threshold )
 {
   rspf_plane_model_t model; memset( &model, 0, sizeof(model) );

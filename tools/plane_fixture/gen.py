@@ -19,6 +19,10 @@ Fixtures (tests/test_planes_cpu.py, tests/test_gpu_planes.py compare every array
                  are kept for a and d only (size).
   planes_gather  a level-0-like and a level-1-like cloud, four hand-made models (one invalid, two overlapping), the index lists of
                  both parameter sets, class / instance ids before and after the relabel.
+  planes_hostile trimmed subsets of the families of tests/hard_planes.py, inputs included: per vote case 512 points x 64 hypotheses,
+                 evaluate_plane_model's counts under three masks and remove_inliers' masks for eight planes; per gather family (257
+                 points) the index lists of both parameter sets and the ids before and after the relabel; the probe room and one tie
+                 cloud with every round of the detection.
 The per-round recordings are replayed from the reference's pieces; every replay is checked here against what the reference's two
 detect functions return for the same input.
 
@@ -70,6 +74,7 @@ def build(ref, tmp):
     L.fx_sample.argtypes = [vp, i64, i32, i32, vp]
     L.fx_score.argtypes = [vp, i64, vp, vp, i32, f32, f32, vp, vp, vp, vp]
     L.fx_remove.argtypes = [vp, i64, vp, vp, vp, f32]
+    L.fx_votes.argtypes = [vp, i64, vp, vp, vp, i32, f32, vp]
     L.fx_gather.argtypes = [vp, vp, i64, vp, i32, f32, f32, i32, i32, vp, vp]
     L.fx_relabel.argtypes = [vp, vp, i64, vp, i32, i32, i32, i32, vp, vp]
     return L
@@ -308,6 +313,59 @@ def write_gather(L, out_dir):
           f"{int(changed.sum())} points relabelled, {size} bytes -> {path}")
 
 
+def write_hostile(L, out_dir):
+    """planes_hostile: the reference on trimmed subsets of the families of tests/hard_planes.py (inputs included)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hard_planes as H
+    out = {}
+    names = []
+    for case in H.vote_cases():
+        c = H.trimmed(case)
+        p = f"votes_{c['name']}_"
+        names.append(c["name"])
+        n, h, thr = len(c["pos"]), len(c["center"]), float(c["dist_threshold"])
+        out.update({p + k: c[k] for k in ("pos", "center", "normal", "dist_threshold")})
+        for mname, m in H.vote_masks(c).items():
+            w = m.astype(np.float64); counts = np.zeros(h, np.int32)
+            L.fx_votes(c["pos"].ctypes.data, n, w.ctypes.data, c["center"].ctypes.data, c["normal"].ctypes.data, h, thr, counts.ctypes.data)
+            out[p + "counts_" + mname] = counts
+        removed = np.zeros((8, n), np.uint8)
+        for j in range(8):                                 # remove_inliers from a full mask, one hypothesis at a time
+            w = np.ones(n, np.float64)
+            L.fx_remove(c["pos"].ctypes.data, n, w.ctypes.data, c["center"][j].ctypes.data, c["normal"][j].ctypes.data, thr)
+            removed[j] = w > 0.01
+        out[p + "removed"] = removed
+    out["vote_cases"] = np.array(names)
+    for name, family in H.GATHER_FAMILIES.items():
+        c = family(257)
+        M, p = c["models"], f"gather_{name}_"
+        m = len(M["center"])
+        out.update({p + "pos": c["pos"], p + "nor": c["nor"], p + "class_before": c["cls"], p + "instance_before": c["inst"]})
+        out.update({p + "model_" + k: v for k, v in M.items()})
+        for pname, dot, dist, cv, ce in (("plain", 0.8, 0.05, 0, 0), ("checked", 0.0, 0.05, 1, 1)):
+            out[p + pname + "_index"], out[p + pname + "_offsets"] = gather(L, c["pos"], c["nor"], M, F(dot), F(dist), cv, ce)
+        cls, inst = c["cls"].copy(), c["inst"].copy()
+        h = Models(M["center"].ctypes.data, M["normal"].ctypes.data, M["axes"].ctypes.data, M["extends"].ctypes.data, M["valid"].ctypes.data,
+                   M["up_dot"].ctypes.data, None)
+        L.fx_relabel(c["pos"].ctypes.data, c["nor"].ctypes.data, len(c["pos"]), C.addressof(h), m, *c["ids"], cls.ctypes.data, inst.ctypes.data)
+        out[p + "class_after"], out[p + "instance_after"] = cls, inst
+        assert ((cls != c["cls"]) | (inst != c["inst"])).any(), name
+    # the probe room: the masks are those of masks() above; the replay they lead to is checked against the reference's two functions
+    r = H.room_with_probes()
+    fm, wm, rounds, want = replay(L, r["pos"], r["nor"], **REF_CALL)
+    assert want["n_floors"] == 1 and want["n_walls"] >= 2 and int(rounds[1]["best"]) == r["best"]
+    out.update(pack("room_", r["pos"], r["nor"], REF_CALL["dot"], REF_CALL["dist"], REF_CALL["count"], fm, wm, rounds, want, normals=False))
+    out.update(room_band=r["band"].astype(np.int32), room_probes=r["probes"].astype(np.int32))
+    # one tie cloud: the detection, rounds included
+    t = H.tie_clouds(("t3",))[0]
+    fm, wm, rounds, want = replay(L, t["pos"], t["nor"], F(0.8), F(0.033), t["count_threshold"])
+    assert len(ties(rounds)) >= 3, ties(rounds)
+    out.update(pack("tie_", t["pos"], t["nor"], 0.8, 0.033, t["count_threshold"], fm, wm, rounds, want, normals=False))
+    path, size = save(out_dir, "hostile", out)
+    print(f"hostile: vote cases {names}, gather families {list(H.GATHER_FAMILIES)}, probe room {len(r['pos'])} points / {len(rounds)} rounds, "
+          f"tie cloud {len(t['pos'])} points, {size} bytes -> {path}")
+
+
 def time_reference(L):
     import plane_timing as T
     pos, nor = T.detect_case()
@@ -321,14 +379,15 @@ def main():
     ap.add_argument("--time", action="store_true", help="only print the reference's CPU time for the detect call of tools/plane_timing.py")
     ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
+    ap.add_argument("--only", default="", help="write this fixture alone (room, quirks, gather, hostile)")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         L = build(a.ref, tmp)
         if a.time:
             return time_reference(L)
-        write_room(L, a.out)
-        write_quirks(L, a.out)
-        write_gather(L, a.out)
+        for name, write in (("room", write_room), ("quirks", write_quirks), ("gather", write_gather), ("hostile", write_hostile)):
+            if a.only in ("", name):
+                write(L, a.out)
 
 
 if __name__ == "__main__":
