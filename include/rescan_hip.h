@@ -80,6 +80,8 @@ rs_hip_cloud_t* rs_hip_cloud_create( const float* pos, const float* nor /* may b
                                      int32_t n, float cell_size );
 void            rs_hip_cloud_destroy( rs_hip_cloud_t* c );
 int32_t         rs_hip_cloud_size( const rs_hip_cloud_t* c );
+/* query tiles of the cloud: runs of at most 64 points of its Hilbert order, what one wave of a search takes */
+int32_t         rs_hip_cloud_tiles( const rs_hip_cloud_t* c );
 /* bytes of HBM held by the cloud */
 int64_t         rs_hip_cloud_bytes( const rs_hip_cloud_t* c );
 /* The cloud's points in the order they were given or produced: 3 * size floats each (either may be NULL; nor only of a cloud

@@ -34,6 +34,7 @@ SIGNATURES = {
     "rs_hip_cloud_destroy": (None, [C.c_void_p]),
     "rs_hip_profile_marker": (C.c_int, []),
     "rs_hip_cloud_size": (C.c_int32, [C.c_void_p]),
+    "rs_hip_cloud_tiles": (C.c_int32, [C.c_void_p]),
     "rs_hip_cloud_bytes": (C.c_int64, [C.c_void_p]),
     "rs_hip_cloud_build_seconds": (C.c_int64, [C.POINTER(C.c_double), C.c_int32]),
     "rs_hip_radius_search": (C.c_int, [C.c_void_p, f32p, C.c_int64, C.c_float, C.c_int32, f32p, i32p, u64p,
@@ -358,6 +359,11 @@ class Cloud:
                       trace=False):
         """rspf__detect_floor then rspf__detect_walls on this cloud (the reference: level 2), see detect_planes()."""
         return detect_planes(self, dot_threshold, dist_threshold, count_threshold, floor_iters, wall_iters, capacity, trace)
+
+    @property
+    def n_tiles(self):
+        """query tiles of the cloud (rs_hip_cloud_tiles): what one wave of a search takes"""
+        return int(load().rs_hip_cloud_tiles(self.handle))
 
     @property
     def nbytes(self):

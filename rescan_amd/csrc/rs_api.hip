@@ -548,6 +548,7 @@ void rs_hip_cloud_destroy( rs_hip_cloud_t* c )
 }
 
 int32_t rs_hip_cloud_size( const rs_hip_cloud_t* c ) { return c ? c->n : 0; }
+int32_t rs_hip_cloud_tiles( const rs_hip_cloud_t* c ) { return c ? c->qview.n_tiles : 0; }
 int64_t rs_hip_cloud_bytes( const rs_hip_cloud_t* c ) { return c ? c->bytes : 0; }
 
 void rs_hip_sincosf_model( const float* x, int64_t n, float* sin_out, float* cos_out )

@@ -114,7 +114,7 @@ struct IcpLaunch
   float   stop_guard;   // (0: off) estimators that are not the reference's own order flag a problem whose |delta err| passes within this of 1e-5 (icp.h:489): the host runs it again in reference order
   int     warm;         // m_slot holds last iteration's matches: use them as starting candidates
   int     seed;         // (when !warm) start from the best usable point of the query's own cell
-  int     bounded_only; // (when warm) phase A only takes tiles whose lanes all start from a candidate; the rest goes straight to the cooperative kernel
+  int     bounded_only; // (when warm) phase A only takes tiles whose lanes all start from a candidate; the rest goes straight to the cooperative kernel.  0 in a call without warm launches: every launch but a call's first is k_icp_corr<true> iff this is set
   int     by_rows;      // (when warm) per-row sweep of the tiles whose lanes all start from a candidate (rs_search.h: sweep_by_rows)
   // certificates issued by every search and consulted when a point has no usable previous match (rs_icp_search.hip: icp_certificate); null = off
   float*  cert_r;       // n_prob x nq

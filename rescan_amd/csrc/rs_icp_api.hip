@@ -10,6 +10,7 @@
 #include "rs_device.h"
 #include "rs_math.h"
 #include "rs_switches.h"
+#include "rs_xcdmap.h"      // the census of icp_debug_after by XCD class
 
 #include <algorithm>
 #include <cfloat>
@@ -500,6 +501,24 @@ void icp_debug_after( IcpCtx& cx, int n_src, int n, int i, float max_dist )
       fprintf( stderr, "[rs_hip dbg]   late finisher: starts at %.1f us, runs %.1f us, shells %u, streamed %u, rank-pass %u, handoff %u\n",
                ( byend[k].start - t0 ) / 100.0, byend[k].ticks / 100.0, byend[k].stages, byend[k].streamed, byend[k].rank_streamed, byend[k].handoff );
   }
+  {
+    // per XCD class of phase A's tile map (rs_xcdmap.h): each XCD dispatches its own class, so a class that ends long after the
+    // others is a launch that ends with slots empty.  Times in us from the launch's first start; a tile handed to the cooperative
+    // kernel without a search (flag 2) has a start and no time.  The list is the one this launch wrote for the next one's front slots.
+    struct Cls { long long tiles = 0; unsigned long long sum = 0, first = ~0ull, last_start = 0, last_end = 0; } cls[XCD_CLASSES];
+    const int nb = xm_blocks( cx.n_waves, RS_PA_WAVES ), map_k = ( cx.L.warm && cx.L.bounded_only ) ? RS_XCD_CHUNK_WARM_LOG2 : RS_XCD_CHUNK_LOG2;      // (this launch's: launch_icp_corr)
+    for( int k = 0; k < cx.n_waves; ++k )
+    {
+      Cls& c = cls[RS_XCD_MAP ? xm_class( k / RS_PA_WAVES, nb, map_k ) : ( k / RS_PA_WAVES ) & ( XCD_CLASSES - 1 )];
+      c.tiles++; c.sum += t[k].ticks; c.first = std::min( c.first, t[k].start ); c.last_start = std::max( c.last_start, t[k].start ); c.last_end = std::max( c.last_end, t[k].start + t[k].ticks );
+    }
+    int fill[XCD_CLASSES] = { 0 };
+    if( cx.L.heavy_out ) (void)hipMemcpy( fill, cx.L.heavy_out, sizeof( fill ), hipMemcpyDeviceToHost );
+    fprintf( stderr, "[rs_hip dbg]   tile map: %s, chunk log2 %d, %d natural blocks\n", RS_XCD_MAP ? ( map_k < 0 ? "contiguous eighths" : "chunks dealt to the classes" ) : "none", map_k, nb );
+    for( int c = 0; c < XCD_CLASSES; ++c )
+      fprintf( stderr, "[rs_hip dbg]   class %d: tiles %lld, tile time %.1f ms, first start %.1f us, last start %.1f us, last end %.1f us, slow-tile list %d of %d\n", c, cls[c].tiles, cls[c].sum / 1e5,
+               cls[c].tiles ? ( cls[c].first - t0 ) / 100.0 : 0.0, cls[c].tiles ? ( cls[c].last_start - t0 ) / 100.0 : 0.0, cls[c].tiles ? ( cls[c].last_end - t0 ) / 100.0 : 0.0, fill[c], HEAVY_PER_CLASS );
+  }
   std::sort( t.begin(), t.end(), []( const Row& a, const Row& b ) { return a.ticks < b.ticks; } );
   for( double q : { 0.5, 0.9, 0.99, 0.999, 1.0 } )
   {
@@ -811,6 +830,7 @@ int icp_align_impl( const rs_hip_cloud_t* src, const rs_hip_cloud_t* const* srcs
   cx.L.stop_guard = ( choice.guard && !fixed_iters && edge ) ? sw_float( SW_STOP_GUARD ) : 0.0f;
   const size_t heavy_words = cx.heavy_words;
   const bool reorder = !sw_flag( SW_NO_LPT ), warm = !sw_flag( SW_NO_WARM );
+  if( !warm ) cx.L.bounded_only = 0;      // (no launch of this call takes the warm form: rs_device.h)
   if( reorder )
   {
     if( ( rc = g_ws.order_a.ensure( heavy_words * 4 ) ) || ( rc = g_ws.order_b.ensure( heavy_words * 4 ) ) ) return rc;

@@ -1429,9 +1429,11 @@ __global__ __launch_bounds__( BLOCK ) void k_chain_moments( IcpLaunch L, ChainBu
 // additions differs — and that order is a function of the launch's shape alone (wave w of workgroup b takes the tiles
 // plain_first + k * plain_stride of its range, lanes are added by wave_sums, the four waves in turn, the workgroups' partials by
 // k_icp_update_wide): two runs give the same bits.
-// The tiles are walked as the search walks them (k_icp_corr: natural_tile): workgroups are dealt round-robin over the 8 XCDs, and
-// XCD class c = b mod 8 takes the c-th eighth of the source's (Hilbert) tile order, so the target lines an XCD gathers are the ones its
-// L2 holds from the search.  RS_PLAIN_XCD=0: plain striding (measurements).
+// The tiles are walked as the warm searches walk them (k_icp_corr<true>: natural_tile): workgroups are dealt round-robin over the 8 XCDs,
+// and XCD class c = b mod 8 takes the c-th eighth of the source's (Hilbert) tile order, so the target lines an XCD gathers are the ones its
+// L2 holds from the search.  (Behind the cold search, which deals the order out in chunks, they are not; this walk stays as it is all the
+// same: which wave takes which tile IS the order of the fp64 additions.  FETCH_SIZE unchanged, profiles/r20.)  RS_PLAIN_XCD=0: plain
+// striding (measurements).
 #ifndef RS_PLAIN_XCD
 #define RS_PLAIN_XCD 1
 #endif

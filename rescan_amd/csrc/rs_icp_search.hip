@@ -1,6 +1,7 @@
 // librescan_hip device code (gfx950, wave64) — the ICP correspondence search (lib/rs/icp.h:306-412)
 #include "rs_search.h"
 #include "rs_icp.h"
+#include "rs_xcdmap.h"
 
 namespace rs {
 
@@ -192,9 +193,6 @@ __device__ __forceinline__ void icp_emit( const IcpLaunch& L, int prob, int tile
 
 
 
-#ifndef RS_XCD_MAP
-#define RS_XCD_MAP 1
-#endif
 // The cold launch (k_icp_corr<false>) sweeps its shells culled to the tile's box grown by a ball, rows from the middle outwards, and
 // its rank pass likewise (rs_search.h: cull_tile).  The warm one-sweep launch (k_icp_corr<true>) and the cooperative
 // kernels have none of it — on the latter it was built and measured slower.  Results keep their bits.  RS_ICP_CULL=0: the unculled
@@ -202,16 +200,16 @@ __device__ __forceinline__ void icp_emit( const IcpLaunch& L, int prob, int tile
 #ifndef RS_ICP_CULL
 #define RS_ICP_CULL 1
 #endif
-// workgroups of phase A's natural part per XCD class (see k_icp_corr)
 // Waves per workgroup of phase A (k_icp_corr).  A workgroup's wave slots and LDS are released when its LAST wave ends, and a
 // warm tile takes its wave 12 us at the median, 17 at the 90th percentile: with four tiles per workgroup a quarter of the slot time
 // was spent waiting for the slowest of four (4 400 of 6 144 slots occupied in the launch's steady state, 5 000-5 200 with one; the
 // concurrent chain's searches 2.22 -> 2.08 ms per step, serial 1.68 -> 1.65: profiles/r02/ab_*experiments.txt).
-#ifndef RS_PA_WAVES
-#define RS_PA_WAVES 1
-#endif
+// (RS_PA_WAVES, default 1: rs_xcdmap.h, whose natural block it is.)
 constexpr int PA_WAVES = RS_PA_WAVES;
-__host__ __device__ inline int icp_blocks_per_xcd( int n_tiles ) { return ( ( n_tiles + PA_WAVES - 1 ) / PA_WAVES + 7 ) / 8; }
+// The tile map of phase A's natural part (rs_xcdmap.h): chunks of 2^k natural blocks of the Hilbert order dealt round-robin to the
+// XCD classes; negative: one contiguous eighth per class.  One k per instantiation: RS_XCD_CHUNK_LOG2 for k_icp_corr<false> (the cold
+// launch), RS_XCD_CHUNK_WARM_LOG2 for k_icp_corr<true> (the warm launches).
+template <bool BOUNDED_ONLY> constexpr int xcd_chunk_log2() { return BOUNDED_ONLY ? RS_XCD_CHUNK_WARM_LOG2 : RS_XCD_CHUNK_LOG2; }
 
 // Phase A: one wave per tile, first shell(s) only; unsettled tiles are queued.
 // Waves per SIMD the register allocation aims at.  5 = 83 / 95 VGPRs (warm / cold instantiation), no scratch; 6 = 80 VGPRs with
@@ -244,14 +242,21 @@ __global__ __launch_bounds__( PA_WAVES * WAVE, BOUNDED_ONLY ? RS_ICP_WARM_OCC : 
   int tile;
   // XCD-aware order of the natural (Hilbert) part: workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8
   // share one), each XCD with its own 4 MB L2.  Walking the tiles in plain order would have every XCD touch every part of
-  // the 32 MB target cloud; instead XCD class c = b mod 8 walks the c-th eighth of the Hilbert order, so an XCD's L2 only
-  // ever sees its own part of the scene (and the seams).  Which XCD a class lands on does not matter.
+  // the 32 MB target cloud; instead every XCD class c = b mod 8 walks a part of the order of its own, so an XCD's L2 only ever
+  // sees its own part of the scene (and the seams).  The warm launches give class c the c-th contiguous eighth of the order (seven
+  // seams).  The cold launch cuts the order into chunks of 2^k blocks and gives class c every eighth chunk from the c-th on
+  // (rs_xcdmap.h): each XCD dispatches its own class independently, and the cold launch's slow tiles — points without a match, the
+  // moved furniture — are clustered in space, so with eighths it ended with the dearest eighth (120 ms of tile time against 65)
+  // while the other XCDs stood empty; a warm launch's tiles cost about the same everywhere, and chunks only cost it seams
+  // (profiles/r20).  Which XCD a class lands on does not matter.
+  constexpr int XCD_K = xcd_chunk_log2<BOUNDED_ONLY>();
   auto natural_tile = [&]( int block ) -> int
   {
 #if RS_XCD_MAP
-    const int per = icp_blocks_per_xcd( L.src.n_tiles );
-    if( ( block >> 3 ) >= per ) return INT_MAX;      // (a multi-source batch's grid is the largest problem's: beyond this problem's own eighths)
-    return ( ( block & 7 ) * per + ( block >> 3 ) ) * PA_WAVES + wib;
+    // (a multi-source batch's grid is the largest problem's: a block beyond this problem's own gives a tile beyond n_tiles)
+    const int nb = xm_blocks( L.src.n_tiles, PA_WAVES );
+    if( xm_beyond( block, nb, XCD_K ) ) return INT_MAX;
+    return xm_block( block, nb, XCD_K ) * PA_WAVES + wib;
 #else
     return block * PA_WAVES + wib;
 #endif
@@ -326,7 +331,9 @@ __global__ __launch_bounds__( PA_WAVES * WAVE, BOUNDED_ONLY ? RS_ICP_WARM_OCC : 
     else if( slow )
     {
 #if RS_XCD_MAP
-      const int c = min( ( tile / PA_WAVES ) / icp_blocks_per_xcd( L.src.n_tiles ), HEAVY_CLASSES - 1 );      // the class whose natural range holds the tile
+      // the class whose natural range holds the tile in the launch that will READ the list — its front slots serve class b mod 8 —
+      // which is k_icp_corr<true> iff the call has warm launches of that form at all (launch_icp_corr; L.bounded_only)
+      const int c = xm_class( tile / PA_WAVES, xm_blocks( L.src.n_tiles, PA_WAVES ), L.bounded_only ? xcd_chunk_log2<true>() : xcd_chunk_log2<false>() );
 #else
       const int c = ( tile / PA_WAVES ) & ( HEAVY_CLASSES - 1 );
 #endif
@@ -443,10 +450,12 @@ void launch_icp_corr( const IcpLaunch& L, hipStream_t st )
   // A launch of a few hundred tiles leaves every wave alone on its SIMD, i.e. latency-bound, and phase A's slowest tile
   // sets its time: such launches skip phase A and give every tile a workgroup straight away (coop_all).
   static_assert( HEAVY_SLOTS % ( 8 * PA_WAVES ) == 0, "the front slots must not shift the XCD class of the natural part" );
-  dim3 grid( ( L.heavy_in ? HEAVY_SLOTS / PA_WAVES : 0 ) + 8 * icp_blocks_per_xcd( L.max_tiles ), L.n_prob );      // (max_tiles: the largest problem's)
+  const bool warm_form = L.warm && L.bounded_only;
+  const int nb = xm_blocks( L.max_tiles, PA_WAVES );      // (max_tiles: the largest problem's)
+  dim3 grid( ( L.heavy_in ? HEAVY_SLOTS / PA_WAVES : 0 ) + ( RS_XCD_MAP ? xm_grid( nb, warm_form ? xcd_chunk_log2<true>() : xcd_chunk_log2<false>() ) : 8 * xm_per_class( nb ) ), L.n_prob );
   if( !L.coop_all )
   {
-    if( L.warm && L.bounded_only ) hipLaunchKernelGGL( k_icp_corr<true>, grid, dim3( PA_WAVES * WAVE ), 0, st, L );
+    if( warm_form ) hipLaunchKernelGGL( k_icp_corr<true>, grid, dim3( PA_WAVES * WAVE ), 0, st, L );
     else                           hipLaunchKernelGGL( k_icp_corr<false>, grid, dim3( PA_WAVES * WAVE ), 0, st, L );
   }
   // the queue length is only known on the device: a fixed grid strides over it

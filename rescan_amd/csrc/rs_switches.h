@@ -12,7 +12,7 @@
 //   at least      the smallest value a SET name can give (NO_MIN: none); the default is not clamped
 //
 // NOT here, because they are compile-time knobs (-D flags of tools/variant.sh): RS_DBG, RS_TAIL_DBG, RS_FAITH_TIMING, RS_FAITH_SPLIT,
-// RS_PLAIN_XCD, RS_PLAIN_MAX_BLOCKS, CH_BUDGET, CH_ITEMS, RS_XCD_MAP, RS_ICP_CULL.  RS_HIP_LIB (which build the Python binding loads) and RS_BENCH_*
+// RS_PLAIN_XCD, RS_PLAIN_MAX_BLOCKS, CH_BUDGET, CH_ITEMS, RS_XCD_MAP, RS_XCD_CHUNK_LOG2, RS_XCD_CHUNK_WARM_LOG2, RS_ICP_CULL.  RS_HIP_LIB (which build the Python binding loads) and RS_BENCH_*
 // belong to rescan_amd/capi.py and bench.py.
 #pragma once
 

@@ -5,6 +5,7 @@
 #   tools/variant.sh taildbg -DRS_TAIL_DBG=1   phase stamps of k_plain_moments / k_icp_update_wide, rs_hip_debug_tail_dump (csrc/rs_tail_dbg.h)
 #   tools/variant.sh s0 -DRS_COOP_STREAM=0     the cooperative ICP kernels with sweep_shell instead of the row table and stream (rs_search.h)
 #   tools/variant.sh s2 -DRS_COOP_PREFETCH=2 [-DRS_COOP_OCC=5]   chunks of a wave in flight / the kernels' waves-per-SIMD target
+#   tools/variant.sh c4 -DRS_XCD_CHUNK_LOG2=4 [-DRS_XCD_CHUNK_WARM_LOG2=4]   phase A's tile map, cold / warm launches: chunks of 2^4 natural blocks; -1: contiguous eighths (rs_xcdmap.h)
 set -e
 cd "$(dirname "$0")/../rescan_amd"
 tag=$1; shift
