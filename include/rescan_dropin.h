@@ -178,6 +178,21 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
                            rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
                            int32_t** out_class, int32_t** out_instance, rsd_mat4_t* xform );
 
+/* The loop of seg2rsdb's pointcloud_to_rsdb (apps/seg2rsdb/main.cpp:80-136) on pointcloud's level-0 arrays: the instances in order
+ * of first appearance, every instance's points cut out in input order and, unless the class of its first point is among
+ * static_classes (the caller's rsdb_is_class_static, which needs the class table), moved by msh_translate( identity, -centroid ) with
+ * centroid.y = 0.  inst_ids / class_of / xforms / poses (one per instance; poses[k] = msh_mat4_inverse( xforms[k] ) is the placement's;
+ * xforms may be NULL) and offsets (one more) have room for `capacity` instances; order, out_pos and out_nor for n points: instance
+ * k's shape is out_pos / out_nor [offsets[k] .. offsets[k + 1]), and its colours, radii, qualities, class and instance ids are the
+ * scan's at order[offsets[k] ..].  Bit for bit the reference's arrays (include/rescan_hip.h: rs_hip_scan_to_objects).  Without a
+ * device the library's host plan answers (rs_hip_split_plan: the same arrays; rsd_device_failures() counts such calls).  Returns the
+ * number of instances, or a negative RS_HIP_E_* code: RS_HIP_E_CAPACITY, with nothing written, when the scan holds more than
+ * `capacity` (or more than 4096) instances. */
+int32_t rsd_scan_to_objects( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const int32_t* class_ids, const int32_t* instance_ids, int64_t n,
+                             const int32_t* static_classes, int32_t n_static, int32_t capacity,
+                             int32_t* inst_ids, int32_t* class_of, int64_t* offsets, int32_t* order,
+                             rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_mat4_t* xforms, rsd_mat4_t* poses );
+
 /* The plane stage of segment_transfer (lib/rs/rs_pointcloud_filters.cpp), on host arrays as the reference holds them.  A plane
  * model crosses as plain arrays, model m at centers[m], normals[m], axes[9m] (msh_mat3_t's data: column-major), extends[4m]
  * (msh_vec4_t's x, y, z, w), valid[m], normal_up_dot[m] = features.normal_up_dot (include/rescan_hip.h).  INTEGRATION.md §3 has

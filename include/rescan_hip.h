@@ -535,6 +535,106 @@ rs_hip_cloud_t* rs_hip_cloud_create_fused( const rs_hip_cloud_t* scan, const int
  * clock (enable != 0: they then synchronise after every stage). */
 void rs_hip_fuse_seconds( double out[5], int32_t enable );
 
+/* ---- scan to object models: the row that opens a sequence ----------------- */
+
+/* seg2rsdb's pointcloud_to_rsdb (apps/seg2rsdb/main.cpp:80-136): a labelled scan cut into one object model per instance.
+ *   table     the distinct values of instance_ids, in order of first appearance (hashtable_keys returns insertion order);
+ *             an id is the int32 itself, negative values included; each comes with its count and the index of its first point
+ *   segment   instance k's points, in input order (rs_pointcloud_copy_by_ids, lib/rs/rs_pointcloud.h:239-297); the object's
+ *             class is the class id of the segment's FIRST point (main.cpp:114), whatever the others carry
+ *   centroid  per axis  double c = 0; c += (double)p[i]  over the segment in order, divided by (double)n, cast to float
+ *             (rs_pointcloud_centroid, :1318-1339); then y = 0 (main.cpp:119)
+ *   xform     identity for an object whose class is among static_classes (the caller's restatement of rsdb_is_class_static,
+ *             which needs a class table); otherwise msh_translate( identity, ( -cx, -0.0f, -cz ) ), and every position goes
+ *             through msh_mat4_vec3_mul( xform, p, 1 ), every normal through ( xform, n, 0 ) — the general product, so a -0.0
+ *             normal component comes out +0.0 and an infinite coordinate makes NaN.  A static object's points are NOT passed
+ *             through the product: their bits are the scan's
+ *   pose      msh_mat4_inverse( xform ), for the identity too
+ * Bit for bit the reference's; where its value is a NaN, a NaN (sign and payload are the adder's or the multiplier's).
+ * The object's bounding box, which the reference computes before the transform and never again, is not an output.
+ *
+ * Refusals, each with a rs_hip_last_error() text and nothing written:
+ *   RS_HIP_E_ARG       n < 0; a required array that is NULL; a static list of negative length, or NULL with n_static > 0
+ *   RS_HIP_E_CAPACITY  more than max_instances (4096) distinct ids; more than 2^31 - 2 points
+ * n = 0 succeeds with no instances. */
+
+/* Where the results go.  Every member but n_instances may be NULL (the plan takes a NULL n_instances too).  With I the number
+ * of instances, which the caller does not know beforehand: arrays "per instance" need room for min( n, max_instances )
+ * entries, offsets for one more.
+ *   inst_ids, counts, first     the table
+ *   offsets                     offsets[k] .. offsets[k + 1]: instance k's part of order, out_pos, out_nor
+ *   order                       n entries: the scan index of every output point, instance-major
+ *   class_of, is_static         per instance
+ *   sums                        3 per instance: the doubles before the division
+ *   centroids                   3 per instance, with y = 0 as the reference leaves it
+ *   xforms, poses               16 per instance, column-major
+ *   out_pos, out_nor            3 n floats: the objects' points, in `order`; out_nor needs the scan's normals
+ * The colour, radius, quality and id arrays follow on the host through order and rs_hip_gather_attributes. */
+typedef struct rs_hip_split_out
+{
+  int32_t* n_instances; int32_t* inst_ids; int64_t* counts; int64_t* first; int64_t* offsets; int32_t* order;
+  int32_t* class_of; int32_t* is_static; double* sums; float* centroids; float* xforms; float* poses;
+  float* out_pos; float* out_nor;
+} rs_hip_split_out_t;
+
+/* The whole of the above by the reference's loops on the HOST; makes no device call.  The checker on machines without a
+ * GPU and the reference of the device route. */
+int rs_hip_split_plan( const float* pos, const float* nor /* may be NULL */, const int32_t* class_ids, const int32_t* instance_ids,
+                       int64_t n, const int32_t* static_classes, int32_t n_static, const rs_hip_split_out_t* out );
+
+/* The table alone, on the device: one atomic per distinct id of a wave into an open-addressed table; only the table comes
+ * back.  inst_ids / counts / first (each may be NULL): room for min( n, max_instances ) entries. */
+int rs_hip_instance_table( const int32_t* instance_ids, int64_t n, int32_t* inst_ids, int64_t* counts, int64_t* first,
+                           int32_t* n_instances );
+
+/* The stable multiway partition, on the device: for every k, order[offsets[k] .. offsets[k + 1]) is what
+ * rs_hip_select_by_ids returns for { inst_ids[k] }.  inst_ids and offsets may be NULL. */
+int rs_hip_split_by_instance( const int32_t* instance_ids, int64_t n, int32_t* inst_ids, int64_t* offsets, int32_t* order,
+                              int32_t* n_instances );
+
+/* The centroid chains alone, on the device: sums[3 k + a] = the sequential fp64 sum of pos[3 order[j] + a] over
+ * j = offsets[k] .. offsets[k + 1] - 1; centroids (may be NULL) the cast quotient BEFORE y = 0.  pos: 3 n floats.  Refused
+ * (RS_HIP_E_ARG): offsets that do not start at 0 or decrease, an entry of order outside [0, n). */
+int rs_hip_segment_centroids( const float* pos, int64_t n, const int32_t* order, const int64_t* offsets, int32_t n_instances,
+                              double* sums, float* centroids /* may be NULL */ );
+
+/* The plan's outputs made on the device end to end (rs_split.hip): table, partition, chains, and one lane per output point
+ * for the transform. */
+int rs_hip_scan_to_objects( const float* pos, const float* nor /* may be NULL */, const int32_t* class_ids,
+                            const int32_t* instance_ids, int64_t n, const int32_t* static_classes, int32_t n_static,
+                            const rs_hip_split_out_t* out );
+
+/* The same from a level-0 cloud with normals, without the points visiting the host: objects[k] (room for
+ * min( size of scan, max_instances ) handles) is instance k's model as an indexed cloud of its own (cell_size as for
+ * rs_hip_cloud_create); rs_hip_cloud_points hands its points out.  class_ids / instance_ids: one per point, in the order the
+ * points were given to the scan.  out: the table, order, class_of, is_static, sums, centroids, xforms and poses; out_pos and
+ * out_nor must be NULL.  The caller owns the clouds and destroys them; a failure part of the way destroys those already made
+ * and returns none. */
+int rs_hip_cloud_split_objects( const rs_hip_cloud_t* scan, const int32_t* class_ids, const int32_t* instance_ids,
+                                const int32_t* static_classes, int32_t n_static, float cell_size,
+                                rs_hip_cloud_t** objects, const rs_hip_split_out_t* out );
+
+/* For tests: the partition's tile (points per column of its [rank][tile] matrix), the largest instance count its LDS route
+ * serves on the calling thread, the refusal cap, and the addends of one step of a centroid chain.  Each may be NULL. */
+void rs_hip_split_layout( int32_t* tile, int32_t* lds_ranks, int32_t* max_instances, int32_t* chain_block );
+
+/* Sets the largest instance count of the partition's LDS route on the calling thread (0: every call takes the sort route;
+ * clamped to 2048) and returns the previous value; a negative argument only reads. */
+int32_t rs_hip_split_lds_ranks( int32_t ranks );
+
+/* Sets the form of the centroid chains on the calling thread — 0 (default): a wave per chain whose steps are order-free where
+ * that is provably exact; 1: a lone lane per chain adding in the reference's order, kept to be measured against — and
+ * returns the previous value; a negative argument only reads.  Both give the same doubles. */
+int32_t rs_hip_split_chains_form( int32_t form );
+
+/* Diagnostic: how many addends the chains of the calling thread's last call added one by one. */
+int64_t rs_hip_split_chains_sequential( void );
+
+/* Diagnostics: where the time of rs_hip_scan_to_objects / rs_hip_cloud_split_objects went on the calling thread since the
+ * last call of this function — table | partition | chains | transform with its copies | index builds, seconds (out may be
+ * NULL) — and whether the next calls keep the clock (enable != 0: they then synchronise after every stage). */
+void rs_hip_split_seconds( double out[5], int32_t enable );
+
 /* ---- neighbourhood graph ------------------------------------------ */
 
 /* rspf_compute_neighborhood (lib/rs/rs_pointcloud_filters.cpp:674-722): K = max_nn self-search

@@ -126,6 +126,17 @@ SIGNATURES = {
     "rs_hip_cloud_create_fused": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                                C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "rs_hip_fuse_seconds": (None, [C.c_void_p, C.c_int32]),
+    "rs_hip_split_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rs_hip_instance_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rs_hip_split_by_instance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rs_hip_segment_centroids": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "rs_hip_scan_to_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rs_hip_cloud_split_objects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "rs_hip_split_layout": (None, [C.POINTER(C.c_int32)] * 4),
+    "rs_hip_split_lds_ranks": (C.c_int32, [C.c_int32]),
+    "rs_hip_split_chains_form": (C.c_int32, [C.c_int32]),
+    "rs_hip_split_chains_sequential": (C.c_int64, []),
+    "rs_hip_split_seconds": (None, [C.c_void_p, C.c_int32]),
     "rs_hip_plane_hypotheses": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rs_hip_plane_votes": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p]),
     "rs_hip_detect_planes": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -355,6 +366,28 @@ class Cloud:
         _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, self._nor.ctypes.data))
         return self, info
 
+    def split_objects(self, class_ids, instance_ids, static_classes=(), cell_size=-1.0):
+        """seg2rsdb's pointcloud_to_rsdb on this level-0 cloud with normals (rs_hip_cloud_split_objects): one indexed cloud per
+        instance, in order of first appearance, the dynamic ones centred; the points never visit the host on the way.  Returns
+        (clouds, info), info as split_plan() returns it without out_pos / out_nor."""
+        lib = load()
+        cls = np.ascontiguousarray(class_ids, np.int32).ravel(); ids = np.ascontiguousarray(instance_ids, np.int32).ravel()
+        if len(cls) != self.n or len(ids) != self.n:
+            raise ValueError("one class id and instance id per point")
+        static = np.ascontiguousarray(static_classes, np.int32).ravel()
+        handles = (C.c_void_p * _split_room(self.n))()
+        info = _split_call(lib.rs_hip_cloud_split_objects, self.n, False, False, self.handle, cls.ctypes.data, ids.ctypes.data,
+                           static.ctypes.data if len(static) else None, len(static), float(cell_size), C.addressof(handles))
+        clouds = []
+        for k in range(info["n_instances"]):
+            c = Cloud.__new__(Cloud)
+            c.handle = handles[k]; c.n = int(info["counts"][k])
+            c._pos = np.zeros((c.n, 3), np.float32); c._nor = np.zeros((c.n, 3), np.float32)
+            clouds.append(c)
+        for c in clouds:
+            _check(lib.rs_hip_cloud_points(c.handle, c._pos.ctypes.data, c._nor.ctypes.data))
+        return clouds, info
+
     def detect_planes(self, dot_threshold=0.8, dist_threshold=0.033, count_threshold=250, floor_iters=2500, wall_iters=5000, capacity=64,
                       trace=False):
         """rspf__detect_floor then rspf__detect_walls on this cloud (the reference: level 2), see detect_planes()."""
@@ -485,6 +518,119 @@ def fuse_seconds(enable=True):
     out = np.zeros(5, np.float64)
     load().rs_hip_fuse_seconds(out.ctypes.data, int(bool(enable)))
     return out
+
+
+class SplitOut(C.Structure):
+    """rs_hip_split_out_t"""
+    _fields_ = [(k, C.c_void_p) for k in ("n_instances", "inst_ids", "counts", "first", "offsets", "order", "class_of", "is_static", "sums",
+                                          "centroids", "xforms", "poses", "out_pos", "out_nor")]
+
+
+def split_layout():
+    """rs_hip_split_layout: dict(tile, lds_ranks, max_instances, chain_block)."""
+    v = [C.c_int32() for _ in range(4)]
+    load().rs_hip_split_layout(*[C.byref(x) for x in v])
+    return dict(tile=v[0].value, lds_ranks=v[1].value, max_instances=v[2].value, chain_block=v[3].value)
+
+
+def split_lds_ranks(ranks=-1):
+    """The largest instance count of the partition's LDS route (rs_hip_split_lds_ranks; 0 forces the sort route); returns the previous."""
+    return load().rs_hip_split_lds_ranks(int(ranks))
+
+
+def split_chains_form(form=-1):
+    """0: the centroid chains' block step, 1: a lone lane per chain (rs_hip_split_chains_form); returns the previous."""
+    return load().rs_hip_split_chains_form(int(form))
+
+
+def split_chains_sequential():
+    """Addends the centroid chains of the last call added one by one (rs_hip_split_chains_sequential)."""
+    return load().rs_hip_split_chains_sequential()
+
+
+def split_seconds(enable=True):
+    """rs_hip_split_seconds: (table, partition, chains, transform, index builds) seconds of scan_to_objects / Cloud.split_objects on
+    this thread since the last call; enable: whether the next calls keep the clock."""
+    out = np.zeros(5, np.float64)
+    load().rs_hip_split_seconds(out.ctypes.data, int(bool(enable)))
+    return out
+
+
+def _split_room(n):
+    return min(max(int(n), 1), split_layout()["max_instances"])
+
+
+def instance_table(instance_ids):
+    """The distinct instance ids in order of first appearance, on the device (rs_hip_instance_table): (inst_ids, counts, first)."""
+    ids = np.ascontiguousarray(instance_ids, np.int32).ravel()
+    m = _split_room(len(ids))
+    inst = np.zeros(m, np.int32); counts = np.zeros(m, np.int64); first = np.zeros(m, np.int64); k = C.c_int32()
+    _check(load().rs_hip_instance_table(ids.ctypes.data, len(ids), inst.ctypes.data, counts.ctypes.data, first.ctypes.data, C.byref(k)))
+    return inst[:k.value].copy(), counts[:k.value].copy(), first[:k.value].copy()
+
+
+def split_by_instance(instance_ids):
+    """The stable multiway partition of a scan by instance id, on the device (rs_hip_split_by_instance): (inst_ids, offsets, order)."""
+    ids = np.ascontiguousarray(instance_ids, np.int32).ravel()
+    m = _split_room(len(ids))
+    inst = np.zeros(m, np.int32); offsets = np.zeros(m + 1, np.int64); order = np.zeros(max(len(ids), 1), np.int32); k = C.c_int32()
+    _check(load().rs_hip_split_by_instance(ids.ctypes.data, len(ids), inst.ctypes.data, offsets.ctypes.data, order.ctypes.data, C.byref(k)))
+    return inst[:k.value].copy(), offsets[:k.value + 1].copy(), order[:len(ids)].copy()
+
+
+def segment_centroids(pos, order, offsets):
+    """rs_pointcloud_centroid's sequential fp64 chains per segment, on the device (rs_hip_segment_centroids): (sums, centroids), each
+    (n_instances, 3); the centroids before y = 0."""
+    pos = _f32(pos).reshape(-1, 3); order = np.ascontiguousarray(order, np.int32).ravel(); offsets = np.ascontiguousarray(offsets, np.int64).ravel()
+    k = max(len(offsets) - 1, 0)
+    sums = np.zeros((k, 3), np.float64); cen = np.zeros((k, 3), np.float32)
+    _check(load().rs_hip_segment_centroids(pos.ctypes.data, len(pos), order.ctypes.data, offsets.ctypes.data, k, sums.ctypes.data, cen.ctypes.data))
+    return sums, cen
+
+
+def _split_call(fn, n, with_points, with_normals, *args):
+    """Allocates every array of rs_hip_split_out_t for n points, calls fn( *args, out ) and trims the arrays to the instances found."""
+    m = _split_room(n)
+    k = C.c_int32()
+    a = dict(inst_ids=np.zeros(m, np.int32), counts=np.zeros(m, np.int64), first=np.zeros(m, np.int64), offsets=np.zeros(m + 1, np.int64),
+             order=np.zeros(max(n, 1), np.int32), class_of=np.zeros(m, np.int32), is_static=np.zeros(m, np.int32), sums=np.zeros((m, 3), np.float64),
+             centroids=np.zeros((m, 3), np.float32), xforms=np.zeros((m, 16), np.float32), poses=np.zeros((m, 16), np.float32))
+    if with_points:
+        a["out_pos"] = np.zeros((max(n, 1), 3), np.float32)
+    if with_normals:
+        a["out_nor"] = np.zeros((max(n, 1), 3), np.float32)
+    out = SplitOut(n_instances=C.addressof(k), **{key: v.ctypes.data for key, v in a.items()})
+    _check(fn(*args, C.addressof(out)))
+    i = k.value
+    r = {key: (v[:n] if key in ("order", "out_pos", "out_nor") else v[:i + 1] if key == "offsets" else v[:i]).copy() for key, v in a.items()}
+    r["n_instances"] = i
+    return r
+
+
+def _split_inputs(pos, nor, class_ids, instance_ids, static_classes):
+    pos = _f32(pos).reshape(-1, 3)
+    nor = None if nor is None else _f32(nor).reshape(-1, 3)
+    cls = np.ascontiguousarray(class_ids, np.int32).ravel(); ids = np.ascontiguousarray(instance_ids, np.int32).ravel()
+    if len(cls) != len(pos) or len(ids) != len(pos) or (nor is not None and len(nor) != len(pos)):
+        raise ValueError("one class id, instance id and normal per point")
+    static = np.ascontiguousarray(static_classes, np.int32).ravel()
+    return pos, nor, cls, ids, static
+
+
+def split_plan(pos, nor, class_ids, instance_ids, static_classes=()):
+    """seg2rsdb's pointcloud_to_rsdb by the reference's loops on the host (rs_hip_split_plan; no device needed): a dict of
+    n_instances, inst_ids, counts, first, offsets, order, class_of, is_static, sums, centroids (y = 0), xforms, poses, out_pos and,
+    with normals, out_nor."""
+    pos, nor, cls, ids, static = _split_inputs(pos, nor, class_ids, instance_ids, static_classes)
+    return _split_call(load().rs_hip_split_plan, len(pos), True, nor is not None, pos.ctypes.data, None if nor is None else nor.ctypes.data,
+                       cls.ctypes.data, ids.ctypes.data, len(pos), static.ctypes.data if len(static) else None, len(static))
+
+
+def scan_to_objects(pos, nor, class_ids, instance_ids, static_classes=()):
+    """The same on the device end to end (rs_hip_scan_to_objects)."""
+    pos, nor, cls, ids, static = _split_inputs(pos, nor, class_ids, instance_ids, static_classes)
+    return _split_call(load().rs_hip_scan_to_objects, len(pos), True, nor is not None, pos.ctypes.data, None if nor is None else nor.ctypes.data,
+                       cls.ctypes.data, ids.ctypes.data, len(pos), static.ctypes.data if len(static) else None, len(static))
 
 
 KNN_MAX_K = 64          # RS_HIP_KNN_MAX_K

@@ -25,6 +25,7 @@
 #include <list>
 #include <memory>
 #include <mutex>
+#include <unordered_set>
 #include <vector>
 
 static_assert( sizeof(rsd_vec3_t) == 12, "msh_vec3_t is 12 bytes" );
@@ -954,6 +955,46 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
   *out_pos = p; *out_nor = q; *out_col = c; *out_radii = r; *out_qual = ql; *out_class = cl; *out_instance = in;
   if( xform ) *xform = x;
   return (int64_t)n;
+}
+
+int32_t rsd_scan_to_objects( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const int32_t* class_ids, const int32_t* instance_ids, int64_t n,
+                             const int32_t* static_classes, int32_t n_static, int32_t capacity,
+                             int32_t* inst_ids, int32_t* class_of, int64_t* offsets, int32_t* order,
+                             rsd_vec3_t* out_pos, rsd_vec3_t* out_nor, rsd_mat4_t* xforms, rsd_mat4_t* poses )
+{
+  if( !pos || !nor || !class_ids || !instance_ids || n < 0 || capacity < 0 || !inst_ids || !class_of || !offsets || !order || !out_pos || !out_nor || !poses )
+  { fprintf( stderr, "rescan_dropin: scan_to_objects: null arrays or a negative count\n" ); return RS_HIP_E_ARG; }
+  // (the library writes per-instance arrays of up to min( n, 4096 ) entries: into vectors first, so that a small capacity is refused
+  //  with nothing written)
+  int32_t max_instances = 0;
+  rs_hip_split_layout( nullptr, nullptr, &max_instances, nullptr );
+  const size_t room = (size_t)std::max<int64_t>( 1, std::min<int64_t>( n, max_instances ) );
+  std::vector<int32_t> ids( room ), cls( room ); std::vector<int64_t> off( room + 1 ); std::vector<float> x( room * 16 ), p( room * 16 );
+  int32_t count = 0;
+  rs_hip_split_out_t out{};
+  out.n_instances = &count; out.inst_ids = ids.data(); out.class_of = cls.data(); out.offsets = off.data(); out.xforms = x.data(); out.poses = p.data();
+  std::vector<int32_t> ord( (size_t)std::max<int64_t>( n, 1 ) );
+  out.order = ord.data();
+  // the distinct ids alone decide the capacity question, on the host: cheap next to the copies below
+  {
+    std::unordered_set<int32_t> seen;
+    for( int64_t i = 0; i < n && (int64_t)seen.size() <= capacity; ++i ) seen.insert( instance_ids[i] );
+    if( (int64_t)seen.size() > capacity ) { fprintf( stderr, "rescan_dropin: scan_to_objects: more than the %d instances there is room for\n", (int)capacity ); return RS_HIP_E_CAPACITY; }
+  }
+  out.out_pos = (float*)out_pos; out.out_nor = (float*)out_nor;
+  int rc = rs_hip_scan_to_objects( (const float*)pos, (const float*)nor, class_ids, instance_ids, n, static_classes, n_static, &out );
+  if( rc == RS_HIP_E_NODEVICE )
+  {
+    if( g_device_failures.fetch_add( 1 ) == 0 )
+      fprintf( stderr, "[rescan_hip] scan_to_objects: no device; this call and any later failing one are answered on the host.  rsd_device_failures() counts them.\n" );
+    rc = rs_hip_split_plan( (const float*)pos, (const float*)nor, class_ids, instance_ids, n, static_classes, n_static, &out );
+  }
+  if( rc ) { complain( "scan_to_objects" ); return rc; }
+  std::memcpy( inst_ids, ids.data(), (size_t)count * 4 ); std::memcpy( class_of, cls.data(), (size_t)count * 4 );
+  std::memcpy( offsets, off.data(), ( (size_t)count + 1 ) * 8 ); std::memcpy( order, ord.data(), (size_t)n * 4 );
+  if( xforms ) std::memcpy( xforms, x.data(), (size_t)count * 64 );
+  std::memcpy( poses, p.data(), (size_t)count * 64 );
+  return count;
 }
 
 int32_t rsd_detect_floor_and_walls( const rsd_vec3_t* pos, const rsd_vec3_t* nor, int64_t n, float dot_threshold, float dist_threshold,
