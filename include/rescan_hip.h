@@ -88,6 +88,36 @@ int64_t         rs_hip_cloud_bytes( const rs_hip_cloud_t* c );
  * with normals).  A copy of what the cloud keeps on the host: no device work.  For clouds that were built on the device
  * (rs_hip_cloud_create_level, rs_hip_cloud_create_resampled) this is how the caller sees their points. */
 int             rs_hip_cloud_points( const rs_hip_cloud_t* c, float* pos, float* nor );
+/* (tests, diagnostics) The two layouts a cloud was built into, read back as they are; changes nothing.  Two calls, sizes first:
+ * with every array pointer NULL the call fills the scalars only (no device work); the caller then sizes its arrays from them, sets
+ * the pointers it wants and calls again.  A pointer left NULL is skipped; nor / qnor only of a cloud with normals (RS_HIP_E_ARG).
+ *   min, cell, inv_cell, dims   the uniform grid; cell = inv_cell = 0 and dims = {1, 1, 1} for the brute layout and an empty cloud.
+ *                               cell is what was used: an explicit or derived cell doubled until the table has at most 48e6 cells
+ *   n_cells                     dims[0] * dims[1] * dims[2]
+ *   occupied                    the occupied-cell count the tile extent limit was derived from (brute layout: an estimate)
+ *   extent_limit                the largest extent of a query tile on any axis (FLT_MAX for an empty cloud)
+ *   cell_start[n_cells + 1]     offsets into the cell-sorted records; cell (x, y, z) has index (z * dims[1] + y) * dims[0] + x
+ *   order[n], qorder[n]         original index of cell-sorted slot s / of Hilbert slot s; by_orig[n]: Hilbert slot of an original index
+ *   tiles[n_tiles + 1]          first Hilbert slot of every query tile, then n
+ *   pos, qpos (nor, qnor)       the 16-byte records of the two layouts as 4 * n words: the point's (normal's) bits and, in the
+ *                               fourth word of a position record, its original index (0 in a normal record)
+ * Inside a cell, and among equal Hilbert keys, points keep the order they were given in.  The bounds min / max are taken over
+ * the finite coordinates of each axis ([0, 0] for an axis that has none).  A point with a coordinate that is not finite is stored
+ * and counted like any other: on that axis it lies in cell 0 (NaN, -Inf) or in cell dims - 1 (+Inf), and no search returns it. */
+typedef struct rs_hip_layout
+{
+  float    min[3], cell, inv_cell;
+  int32_t  dims[3];
+  int64_t  n, n_cells, occupied;
+  float    extent_limit;
+  int32_t  n_tiles, has_normals;
+  uint32_t *cell_start;
+  int32_t  *order, *qorder;
+  uint32_t *tiles;
+  int32_t  *by_orig;
+  uint32_t *pos, *qpos, *nor, *qnor;
+} rs_hip_layout_t;
+int             rs_hip_cloud_layout( const rs_hip_cloud_t* c, rs_hip_layout_t* out );
 /* (diagnostics) Where cloud construction went, in seconds of the calling threads' wall clock, summed over every cloud the process
  * built since the last reset: out[0] host copy of the arrays, [1] upload + bounds, [2] cell index (sort by cell, offset table),
  * [3] Hilbert order + tiles.  Returns the number of clouds counted; reset != 0 clears the counters. */

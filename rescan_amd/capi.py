@@ -36,6 +36,7 @@ SIGNATURES = {
     "rs_hip_cloud_size": (C.c_int32, [C.c_void_p]),
     "rs_hip_cloud_tiles": (C.c_int32, [C.c_void_p]),
     "rs_hip_cloud_bytes": (C.c_int64, [C.c_void_p]),
+    "rs_hip_cloud_layout": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rs_hip_cloud_build_seconds": (C.c_int64, [C.POINTER(C.c_double), C.c_int32]),
     "rs_hip_radius_search": (C.c_int, [C.c_void_p, f32p, C.c_int64, C.c_float, C.c_int32, f32p, i32p, u64p,
                                        C.POINTER(C.c_uint64)]),
@@ -176,6 +177,14 @@ class IsectShape(C.Structure):
 class ProposeTrace(C.Structure):
     """rs_hip_propose_trace_t"""
     _fields_ = [("n_scored", C.c_void_p), ("n_kept", C.c_void_p), ("n_proposed", C.c_void_p)]
+
+
+class Layout(C.Structure):
+    """rs_hip_layout_t"""
+    ARRAYS = ("cell_start", "order", "qorder", "tiles", "by_orig", "pos", "qpos", "nor", "qnor")
+    _fields_ = ([("min", C.c_float * 3), ("cell", C.c_float), ("inv_cell", C.c_float), ("dims", C.c_int32 * 3),
+                 ("n", C.c_int64), ("n_cells", C.c_int64), ("occupied", C.c_int64), ("extent_limit", C.c_float),
+                 ("n_tiles", C.c_int32), ("has_normals", C.c_int32)] + [(k, C.c_void_p) for k in ARRAYS])
 
 
 class Placement(C.Structure):
@@ -392,6 +401,25 @@ class Cloud:
                       trace=False):
         """rspf__detect_floor then rspf__detect_walls on this cloud (the reference: level 2), see detect_planes()."""
         return detect_planes(self, dot_threshold, dist_threshold, count_threshold, floor_iters, wall_iters, capacity, trace)
+
+    def layout(self):
+        """The two layouts as the build left them (rs_hip_cloud_layout): a dict of the scalars min, cell, inv_cell, dims, n, n_cells,
+        occupied, extent_limit, n_tiles and the arrays cell_start, order, qorder, tiles, by_orig, pos, qpos — the records as (n, 4)
+        uint32 — with nor and qnor for a cloud with normals."""
+        lib = load()
+        L = Layout()
+        _check(lib.rs_hip_cloud_layout(self.handle, C.addressof(L)))
+        n, dt = int(L.n), {"order": np.int32, "qorder": np.int32, "by_orig": np.int32}
+        shapes = dict(cell_start=(L.n_cells + 1,), order=(n,), qorder=(n,), tiles=(L.n_tiles + 1,), by_orig=(n,), pos=(n, 4), qpos=(n, 4))
+        if L.has_normals:
+            shapes.update(nor=(n, 4), qnor=(n, 4))
+        out = {k: np.zeros(shape, dt.get(k, np.uint32)) for k, shape in shapes.items()}
+        for k, a in out.items():
+            setattr(L, k, a.ctypes.data)
+        _check(lib.rs_hip_cloud_layout(self.handle, C.addressof(L)))
+        out.update(min=np.array(L.min[:], np.float32), cell=np.float32(L.cell), inv_cell=np.float32(L.inv_cell), dims=np.array(L.dims[:], np.int32),
+                   n=n, n_cells=int(L.n_cells), occupied=int(L.occupied), extent_limit=np.float32(L.extent_limit), n_tiles=int(L.n_tiles))
+        return out
 
     @property
     def n_tiles(self):

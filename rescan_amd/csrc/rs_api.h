@@ -94,6 +94,8 @@ struct rs_hip_cloud
   std::vector<float> h_pos, h_nor;  // original-order host copies (AoS)
   float nor_max = 1.0f;             // max |normal| (bounds how fast a gate value can change with the query normal)
   float cell = 0.0f;
+  int64_t occupied = 0;             // occupied cells as handed to query_extent_limit (brute layout: the estimate of a 0.1 m grid)
+  float extent_limit = 0.0f;        // the tile extent limit the query layout was cut with
   int64_t bytes = 0;
   // as an ICP source whose centroid chains gave a problem up (sums that hover around zero: rs_hip_icp_align_batch): the next calls
   // this many go straight to pass 2 of the replay instead of paying for the attempt first

@@ -8,6 +8,7 @@
 
 #include "../../include/rescan_hip.h"
 #include "rs_api.h"
+#include "rs_buildplan.h"
 #include "rs_device.h"
 #include "rs_host.h"
 #include "rs_math.h"
@@ -153,18 +154,9 @@ namespace {
 // ---- query layout ---------------------------------------------------------------------------
 // (Hilbert order + greedy tiling are computed on the device: rs_build.hip.)
 
-// Tile extent limit from the cloud's own sampling density: a full tile of 64 surface samples
-// spans about 8 sample spacings; allow half as much again, and never less than 0.25 m.
-float query_extent_limit( int32_t n, size_t occupied_cells, float cell )
-{
-  if( n <= 0 || occupied_cells == 0 || !( cell > 0.0f ) ) return FLT_MAX;
-  float per_cell = (float)n / (float)occupied_cells;
-  float spacing = cell / std::sqrt( std::max( per_cell, 1.0f ) );
-  // ... and never more than 0.3 m: a sparse cloud (a subsampled level, a random subset) searched in a denser one would
-  // otherwise get tiles whose box is mostly the empty space between its points (1000 points against a 200 k scan:
-  // 404 -> 60 us per ICP iteration with the cap)
-  return std::min( sw_float( SW_TILE_EXTENT_MAX ), std::max( 0.25f, 12.0f * spacing ) );
-}
+// (The tile extent limit, from the cloud's own sampling density: query_extent_limit, rs_buildplan.h.  Its cap, RS_HIP_TILE_EXTENT_MAX:
+//  a sparse cloud (a subsampled level, a random subset) searched in a denser one would otherwise get tiles whose box is mostly the
+//  empty space between its points — 1000 points against a 200 k scan: 404 -> 60 us per ICP iteration with the cap.)
 
 } // namespace
 
@@ -365,7 +357,7 @@ rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, int32_t n
     CC( hipStreamSynchronize( g_stream ) );
     auto dec = []( unsigned u ) { unsigned b = ( u & 0x80000000u ) ? ( u ^ 0x80000000u ) : ~u; float f; std::memcpy( &f, &b, 4 ); return f; };
     for( int a = 0; a < 3; ++a ) { mn[a] = dec( got[a] ); mx[a] = dec( got[3 + a] ); }
-    for( int a = 0; a < 3; ++a ) { if( !( mx[a] >= mn[a] ) || !std::isfinite( mn[a] ) || !std::isfinite( mx[a] ) ) { mn[a] = 0; mx[a] = 0; } }
+    bp_sanitise_bounds( mn, mx );           // (the kernel took the finite coordinates only; an axis without one: [0, 0])
     if( nor )
     {
       float n2; std::memcpy( &n2, &got[6], 4 );
@@ -381,45 +373,37 @@ rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, int32_t n
     cell_size = 0.1f;
     if( n > 0 )
     {
-      float ext = std::max( mx[0] - mn[0], std::max( mx[1] - mn[1], mx[2] - mn[2] ) );
-      float c0 = std::min( 0.1f, std::max( ext / 64.0f, 1e-4f ) );
-      for( int attempt = 0; attempt < 8; ++attempt, c0 *= 2.0f )
+      float c0 = bp_trial_first_cell( mn, mx );
+      for( int attempt = 0; attempt < RS_BP_TRIAL_ATTEMPTS; ++attempt, c0 *= 2.0f )
       {
-        const float inv = 1.0f / c0;
-        unsigned long long td[3]; double cells = 1.0;
-        for( int a = 0; a < 3; ++a ) { td[a] = (unsigned long long)std::max( 0.0f, floorf( ( mx[a] - mn[a] ) * inv ) ) + 2ull; cells *= (double)td[a]; }
-        if( cells > 1073741824.0 && attempt < 7 ) continue;          // trial grid too fine to count (huge, sparse extent): coarsen
-        float per_cell = 4.0f;
-        if( cells <= 1073741824.0 )
+        const TrialGrid tg = bp_trial_grid( mn, mx, c0 );
+        if( !tg.countable() && attempt < RS_BP_TRIAL_ATTEMPTS - 1 ) continue;          // trial grid too fine to count (huge, sparse extent): coarsen
+        float per_cell = RS_BP_PER_CELL_WANTED;
+        if( tg.countable() )
         {
-          const size_t words = (size_t)( cells / 32.0 ) + 2;
+          const size_t words = tg.words();
           if( W.bld_bits.ensure( words * 4 ) ) return failrc( "workspace allocation failed" );
           CC( hipMemsetAsync( W.bld_bits.p, 0, words * 4, g_stream ) );
           CC( hipMemsetAsync( d_small, 0, 4, g_stream ) );
-          launch_build_mark( d_raw, n, mn, inv, td[1], td[2], W.bld_bits.as<uint32_t>(), g_stream );
+          launch_build_mark( d_raw, n, mn, tg.inv, tg.top, tg.td[1], tg.td[2], W.bld_bits.as<uint32_t>(), g_stream );
           launch_popcount( W.bld_bits.as<uint32_t>(), (int)words, (int*)d_small, g_stream );
           int occ = 0;
           CC( hipMemcpyAsync( &occ, d_small, 4, hipMemcpyDeviceToHost, g_stream ) );
           CC( hipStreamSynchronize( g_stream ) );
-          per_cell = (float)n / (float)std::max( 1, occ );
+          per_cell = bp_per_cell( n, occ );
         }
-        if( per_cell >= 4.0f || attempt == 7 ) { cell_size = 2.0f * c0 / std::sqrt( std::max( per_cell, 1.0f ) ); break; }
+        if( per_cell >= RS_BP_PER_CELL_WANTED || attempt == RS_BP_TRIAL_ATTEMPTS - 1 ) { cell_size = bp_auto_cell_of( per_cell, c0 ); break; }
       }
-      cell_size = std::min( std::max( cell_size * sw_float( SW_AUTO_CELL_SCALE ), 0.005f ), 2.0f );
+      cell_size = bp_auto_cell_scaled( cell_size, sw_float( SW_AUTO_CELL_SCALE ) );
     }
   }
   int dims[3] = { 1, 1, 1 };
   float inv_cell = 0.0f, cell = cell_size;
   if( cell_size > 0.0f && n > 0 )
   {
-    for( ;; )
-    {
-      double cells = 1.0;
-      for( int a = 0; a < 3; ++a ) { dims[a] = (int)std::floor( ( (double)mx[a] - (double)mn[a] ) / (double)cell ) + 1; cells *= dims[a]; }
-      if( cells <= 48.0e6 ) break;
-      cell *= 2.0f;                          // keep the dense offset table below ~200 MB
-    }
-    inv_cell = 1.0f / cell;
+    // (in double before any cast: an extent of any size is coarsened into the table; one that overflows a float gets the brute layout)
+    if( bp_table_dims( mn, mx, cell, dims ) ) inv_cell = 1.0f / cell;
+    else cell_size = cell = 0.0f;
   }
   c->cell = ( cell_size > 0.0f ) ? cell : 0.0f;
   const size_t n_cells = (size_t)dims[0] * dims[1] * dims[2];
@@ -462,17 +446,16 @@ rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, int32_t n
   if( !( cell_size > 0.0f ) )
   {
     // brute layout has one cell: estimate the occupancy of a 0.1 m grid instead
-    double vol_cells = 1.0; for( int a = 0; a < 3; ++a ) vol_cells *= std::floor( ( (double)mx[a] - mn[a] ) / 0.1 ) + 1.0;
-    occupied = (size_t)std::max( 1.0, std::min( (double)n, std::pow( vol_cells, 2.0 / 3.0 ) ) );
+    occupied = bp_brute_occupied( n, mn, mx );
   }
+  c->occupied = (int64_t)occupied;
+  c->extent_limit = query_extent_limit( n, occupied, lim_cell, sw_float( SW_TILE_EXTENT_MAX ) );
   CC( hipMalloc( (void**)&c->d_qpos, pb ) );
   if( nor ) CC( hipMalloc( (void**)&c->d_qnor, pb ) );
   int n_tiles = 0;
   if( n > 0 )
   {
-    float ext = 0.0f;
-    for( int a = 0; a < 3; ++a ) { float e = mx[a] - mn[a]; if( std::isfinite( e ) && e > ext ) ext = e; }
-    const float scale = ext > 0.0f ? 1024.0f / ext : 0.0f;
+    const float scale = bp_hilbert_scale( mn, mx );
     launch_build_hilbert( d_raw, n, mn, scale, k0, v0, g_stream );
     if( build_sort_pairs( W.bld_tmp.p, tmp_bytes, k0, k1, v0, v2, n, 30, g_stream ) ) return failrc( "device sort failed" );
     launch_build_gather( d_raw, d_rawn, v2, n, c->d_qpos, c->d_qnor, g_stream );
@@ -481,7 +464,7 @@ rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, int32_t n
     // tile starts: flags -> exclusive scan -> scatter
     uint32_t* flags = k0; uint32_t* scanned = k1;
     CC( hipMemsetAsync( flags + n, 0, 4, g_stream ) );
-    launch_build_tile_flags( c->d_qpos, n, query_extent_limit( n, occupied, lim_cell ), flags, v0, v1, g_stream );   // (order / v1 is on the host by now)
+    launch_build_tile_flags( c->d_qpos, n, c->extent_limit, flags, v0, v1, g_stream );   // (order / v1 is on the host by now)
     if( build_exclusive_scan( W.bld_tmp.p, tmp_bytes, flags, scanned, (size_t)n + 1, g_stream ) ) return failrc( "device scan failed" );
     unsigned total = 0;
     CC( hipMemcpyAsync( &total, scanned + n, 4, hipMemcpyDeviceToHost, g_stream ) );
@@ -550,6 +533,35 @@ void rs_hip_cloud_destroy( rs_hip_cloud_t* c )
 int32_t rs_hip_cloud_size( const rs_hip_cloud_t* c ) { return c ? c->n : 0; }
 int32_t rs_hip_cloud_tiles( const rs_hip_cloud_t* c ) { return c ? c->qview.n_tiles : 0; }
 int64_t rs_hip_cloud_bytes( const rs_hip_cloud_t* c ) { return c ? c->bytes : 0; }
+
+// What the build left, read back as it is: changes nothing and books no profile span.
+int rs_hip_cloud_layout( const rs_hip_cloud_t* c, rs_hip_layout_t* out )
+{
+  if( !c || !out ) { set_err( "cloud_layout: no cloud, or nowhere to write" ); return RS_HIP_E_ARG; }
+  if( ( out->nor || out->qnor ) && !c->has_nor ) { set_err( "cloud_layout: normals asked of a cloud without them" ); return RS_HIP_E_ARG; }
+  const GridView& v = c->view;
+  out->min[0] = v.minx; out->min[1] = v.miny; out->min[2] = v.minz; out->cell = v.cell; out->inv_cell = v.inv_cell;
+  out->dims[0] = v.w; out->dims[1] = v.h; out->dims[2] = v.d;
+  out->n = c->n; out->n_cells = (int64_t)v.w * v.h * v.d; out->occupied = c->occupied; out->extent_limit = c->extent_limit;
+  out->n_tiles = c->qview.n_tiles; out->has_normals = c->has_nor ? 1 : 0;
+  const size_t n = (size_t)c->n;
+  if( out->order && n ) std::memcpy( out->order, c->order.data(), n * 4 );
+  if( out->qorder && n ) std::memcpy( out->qorder, c->qorder.data(), n * 4 );
+  if( !( out->cell_start || out->tiles || out->by_orig || out->pos || out->qpos || out->nor || out->qnor ) ) return RS_HIP_OK;
+  int rc = ensure_ready(); if( rc ) return rc;
+  HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
+  if( out->cell_start ) HIP_TRY( hipMemcpy( out->cell_start, c->d_cell_start, ( (size_t)out->n_cells + 1 ) * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+  if( out->tiles ) HIP_TRY( hipMemcpy( out->tiles, c->d_tiles, ( (size_t)out->n_tiles + 1 ) * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+  if( n )
+  {
+    if( out->by_orig ) HIP_TRY( hipMemcpy( out->by_orig, c->d_qby_orig, n * 4, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+    if( out->pos ) HIP_TRY( hipMemcpy( out->pos, c->d_pos, n * 16, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+    if( out->qpos ) HIP_TRY( hipMemcpy( out->qpos, c->d_qpos, n * 16, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+    if( out->nor ) HIP_TRY( hipMemcpy( out->nor, c->d_nor, n * 16, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+    if( out->qnor ) HIP_TRY( hipMemcpy( out->qnor, c->d_qnor, n * 16, hipMemcpyDeviceToHost ), RS_HIP_E_RUNTIME );
+  }
+  return RS_HIP_OK;
+}
 
 void rs_hip_sincosf_model( const float* x, int64_t n, float* sin_out, float* cos_out )
 {

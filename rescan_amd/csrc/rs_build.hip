@@ -8,6 +8,7 @@
 // points inside a cell, nor the tiling.  The one expression that must agree with the search kernels is
 // the cell coordinate of a stored point (cell_of_dev; rs_search.h: axis_range covers it with a 0.01-cell margin).
 #include "rs_device.h"
+#include "rs_buildplan.h"
 #include <hipcub/hipcub.hpp>
 #include <cfloat>
 #include <algorithm>
@@ -26,7 +27,7 @@ __global__ __launch_bounds__( B_BLOCK ) void k_build_bounds( const float* pos, c
   for( int i = blockIdx.x * B_BLOCK + threadIdx.x; i < n; i += gridDim.x * B_BLOCK )
   {
 #pragma unroll
-    for( int a = 0; a < 3; ++a ) { const float v = pos[3 * (size_t)i + a]; if( v < lo[a] ) lo[a] = v; if( v > hi[a] ) hi[a] = v; }   // NaN never wins, as on the host
+    for( int a = 0; a < 3; ++a ) bp_bounds_take( pos[3 * (size_t)i + a], lo[a], hi[a] );   // over the finite coordinates: neither NaN nor ±Inf wins
     if( nor ) { const float x = nor[3 * (size_t)i], y = nor[3 * (size_t)i + 1], z = nor[3 * (size_t)i + 2]; const float l = x * x + y * y + z * z; if( !( l <= n2 ) ) n2 = l; }   // NaN/inf propagate: certificates then stay off
   }
   for( int o = 32; o > 0; o >>= 1 )
@@ -43,34 +44,24 @@ __global__ __launch_bounds__( B_BLOCK ) void k_build_bounds( const float* pos, c
   }
 }
 
-// occupancy of a trial grid: one bit per cell
-__global__ __launch_bounds__( B_BLOCK ) void k_build_mark( const float* pos, int n, float mx, float my, float mz, float inv, unsigned long long db, unsigned long long dc, uint32_t* bits )
+// occupancy of a trial grid: one bit per cell (rs_buildplan.h: every point's cell is inside the grid, whatever its coordinates)
+__global__ __launch_bounds__( B_BLOCK ) void k_build_mark( const float* pos, int n, float mx, float my, float mz, float inv, float tx, float ty, float tz,
+                                                           unsigned long long db, unsigned long long dc, uint32_t* bits )
 {
   const int i = blockIdx.x * B_BLOCK + threadIdx.x;
   if( i >= n ) return;
-  const unsigned long long a = (unsigned long long)fmaxf( 0.0f, floorf( ( pos[3 * (size_t)i] - mx ) * inv ) ),
-                           b = (unsigned long long)fmaxf( 0.0f, floorf( ( pos[3 * (size_t)i + 1] - my ) * inv ) ),
-                           c = (unsigned long long)fmaxf( 0.0f, floorf( ( pos[3 * (size_t)i + 2] - mz ) * inv ) );
-  const unsigned long long id = ( a * db + b ) * dc + c;
+  const unsigned long long id = bp_trial_cell( pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], mx, my, mz, inv, tx, ty, tz, db, dc );
   atomicOr( bits + ( id >> 5 ), 1u << ( id & 31 ) );
 }
 
-// cell coordinate of a stored point along one axis (the search kernels' axis_range covers this expression with a 0.01-cell margin)
-__device__ __forceinline__ int cell_of_dev( float v, float gmin, float inv_cell, int dim )
-{
-  float c = floorf( ( v - gmin ) * inv_cell );
-  if( !( c >= 0.0f ) ) c = 0.0f;
-  if( c > (float)( dim - 1 ) ) c = (float)( dim - 1 );
-  return (int)c;
-}
-
+// (cell_of_dev, the cell coordinate of a stored point along one axis: rs_buildplan.h)
 __global__ __launch_bounds__( B_BLOCK ) void k_build_cellids( const float* pos, int n, float mx, float my, float mz, float inv_cell, int w, int h, int d,
                                                               uint32_t* cid, uint32_t* iota, uint32_t* counts )
 {
   const int i = blockIdx.x * B_BLOCK + threadIdx.x;
   if( i >= n ) return;
   const int cx = cell_of_dev( pos[3 * (size_t)i], mx, inv_cell, w ), cy = cell_of_dev( pos[3 * (size_t)i + 1], my, inv_cell, h ), cz = cell_of_dev( pos[3 * (size_t)i + 2], mz, inv_cell, d );
-  const uint32_t id = (uint32_t)( ( (size_t)cz * h + cy ) * w + cx );
+  const uint32_t id = bp_cell_id( cx, cy, cz, w, h );
   cid[i] = id; iota[i] = (uint32_t)i;
   atomicAdd( counts + id, 1u );
 }
@@ -92,32 +83,7 @@ __global__ __launch_bounds__( B_BLOCK ) void k_build_count_runs( const uint32_t*
   if( ( threadIdx.x & 63 ) == 0 && c ) atomicAdd( out, c );
 }
 
-// Index of a cell on a 3-D Hilbert curve with `bits` bits per axis (Skilling's transpose form)
-__device__ __forceinline__ uint32_t hilbert3_dev( uint32_t x, uint32_t y, uint32_t z, int bits )
-{
-  uint32_t X[3] = { x, y, z };
-  const uint32_t M = 1u << ( bits - 1 );
-  for( uint32_t Q = M; Q > 1; Q >>= 1 )
-  {
-    const uint32_t P = Q - 1;
-#pragma unroll
-    for( int i = 0; i < 3; ++i )
-    {
-      if( X[i] & Q ) X[0] ^= P;
-      else { const uint32_t t = ( X[0] ^ X[i] ) & P; X[0] ^= t; X[i] ^= t; }
-    }
-  }
-  X[1] ^= X[0]; X[2] ^= X[1];
-  uint32_t t = 0;
-  for( uint32_t Q = M; Q > 1; Q >>= 1 ) if( X[2] & Q ) t ^= Q - 1;
-  X[0] ^= t; X[1] ^= t; X[2] ^= t;
-  uint32_t h = 0;
-  for( int b = bits - 1; b >= 0; --b )
-#pragma unroll
-    for( int i = 0; i < 3; ++i ) h = ( h << 1 ) | ( ( X[i] >> b ) & 1u );
-  return h;
-}
-
+// (hilbert3_dev, Skilling's transpose form, and a coordinate's Hilbert cell: rs_buildplan.h)
 __global__ __launch_bounds__( B_BLOCK ) void k_build_hilbert( const float* pos, int n, float mx, float my, float mz, float scale, uint32_t* key, uint32_t* iota )
 {
   const int i = blockIdx.x * B_BLOCK + threadIdx.x;
@@ -125,13 +91,7 @@ __global__ __launch_bounds__( B_BLOCK ) void k_build_hilbert( const float* pos, 
   const float mn[3] = { mx, my, mz };
   uint32_t c[3];
 #pragma unroll
-  for( int a = 0; a < 3; ++a )
-  {
-    float f = ( pos[3 * (size_t)i + a] - mn[a] ) * scale;
-    if( !( f >= 0.0f ) ) f = 0.0f;
-    if( f > 1023.0f ) f = 1023.0f;
-    c[a] = (uint32_t)f;
-  }
+  for( int a = 0; a < 3; ++a ) c[a] = bp_hilbert_axis( pos[3 * (size_t)i + a], mn[a], scale );
   key[i] = hilbert3_dev( c[0], c[1], c[2], 10 );
   iota[i] = (uint32_t)i;
 }
@@ -188,9 +148,9 @@ void launch_build_bounds( const float* pos3, const float* nor3, int n, unsigned*
 {
   hipLaunchKernelGGL( k_build_bounds, dim3( std::min( 1024u, blocks_for( n ) ) ), dim3( B_BLOCK ), 0, st, pos3, nor3, n, out8 );
 }
-void launch_build_mark( const float* pos3, int n, const float mn[3], float inv, unsigned long long db, unsigned long long dc, uint32_t* bits, hipStream_t st )
+void launch_build_mark( const float* pos3, int n, const float mn[3], float inv, const float top[3], unsigned long long db, unsigned long long dc, uint32_t* bits, hipStream_t st )
 {
-  hipLaunchKernelGGL( k_build_mark, dim3( blocks_for( n ) ), dim3( B_BLOCK ), 0, st, pos3, n, mn[0], mn[1], mn[2], inv, db, dc, bits );
+  hipLaunchKernelGGL( k_build_mark, dim3( blocks_for( n ) ), dim3( B_BLOCK ), 0, st, pos3, n, mn[0], mn[1], mn[2], inv, top[0], top[1], top[2], db, dc, bits );
 }
 void launch_build_cellids( const float* pos3, int n, const float mn[3], float inv_cell, const int dims[3], uint32_t* cid, uint32_t* iota, uint32_t* counts, hipStream_t st )
 {

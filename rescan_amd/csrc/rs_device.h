@@ -304,7 +304,7 @@ void launch_coverage( const CoverageLaunch& L, hipStream_t st );
 
 // Device-side cloud construction (rs_build.hip)
 void   launch_build_bounds( const float* pos3, const float* nor3, int n, unsigned* out8, hipStream_t st );
-void   launch_build_mark( const float* pos3, int n, const float mn[3], float inv, unsigned long long db, unsigned long long dc, uint32_t* bits, hipStream_t st );
+void   launch_build_mark( const float* pos3, int n, const float mn[3], float inv, const float top[3], unsigned long long db, unsigned long long dc, uint32_t* bits, hipStream_t st );
 void   launch_build_cellids( const float* pos3, int n, const float mn[3], float inv_cell, const int dims[3], uint32_t* cid, uint32_t* iota, uint32_t* counts, hipStream_t st );
 void   launch_build_gather( const float* pos3, const float* nor3, const uint32_t* order, int n, float4* spos, float4* snor, hipStream_t st );
 void   launch_build_count_runs( const uint32_t* sorted, int n, int* out, hipStream_t st );

@@ -115,6 +115,19 @@ def test_fails_loudly_without_gpu(lib):
     assert rc == -1 and b"no HIP device" in lib.rs_hip_last_error()
 
 
+def test_cloud_layout_refuses_without_a_cloud(lib):
+    """rs_hip_cloud_layout needs a cloud, and a cloud needs a device: without either it answers RS_HIP_E_ARG, names itself in the
+    error text and leaves the caller's struct alone — before it touches the HIP runtime."""
+    from rescan_amd import capi
+    L = capi.Layout()
+    L.n_tiles = 77
+    assert lib.rs_hip_cloud_layout(None, ctypes.addressof(L)) == -2 and b"cloud_layout" in lib.rs_hip_last_error()
+    assert L.n_tiles == 77 and not L.cell_start
+    assert lib.rs_hip_cloud_layout(None, None) == -2
+    assert [k for k, _ in capi.Layout._fields_][-len(capi.Layout.ARRAYS):] == list(capi.Layout.ARRAYS)
+    assert ctypes.sizeof(capi.Layout) == 5 * 4 + 3 * 4 + 3 * 8 + 3 * 4 + 4 + 9 * 8      # (one word of padding before the pointers)
+
+
 def test_spin_flags_hand_work_between_threads():
     """tools/benchaux (the harness's own helper library, NOT the product ABI): a worker thread and the caller ping-pong through two
     int32 flags without ever sleeping in a queue; a wait that cannot succeed times out; and none of these helpers is exported by
