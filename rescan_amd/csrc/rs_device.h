@@ -132,7 +132,7 @@ struct IcpLaunch
   int     heavy_streamed;   // a tile that streamed at least this many candidates is listed
   int     heavy_total;      // warm launch: a bounded tile swept tile-wide (boxes too tall for the per-row sweep) is handed off too when the first 64 cell rows of its box hold this many candidates (0: never)
   int     heavy_handoff;    // ... and one that streamed this many in a warm launch goes to the cooperative kernel from the next iteration on (flag 2)
-  // reference-order estimator (rs_icp_estimate.hip: k_icp_faithful); faith == null: fp64 moments
+  // reference-order estimator (rs_icp_faithful.hip: k_icp_faithful); faith == null: fp64 moments
   const int* by_orig;   // original source index -> query slot (null: identity)
   float*  faith;        // n_prob x FAITH_REC x nq: the correspondences in the source's own order
   // "exact centroids" estimator (large sources): the fp64 moments, but the seven sums behind the two weighted centroids
@@ -140,14 +140,14 @@ struct IcpLaunch
   // and launch_icp_exact_centroids_from_records
   int     exact_centroids;
   const double* centroid_totals;   // n_prob x 3 x ICP_NMOM (ReplayBufs::totals): [ICP_NMOM + 0..6] = the seven chain totals
-  // ... and their fast form (rs_icp_estimate.hip: "grid chains"): every search writes one 48-byte record per source point at the point's
+  // ... and their fast form (rs_icp_chain.hip: "grid chains"): every search writes one 48-byte record per source point at the point's
   // ORIGINAL index — {p.xyz, dist² (< 0: no match)} {q.xyz, dot} {n.xyz, -} — which the estimator's kernels then read in the
   // reference's own order, coalesced (null: not wanted)
   float4* rec;                     // n_prob x n x REC_F4
 };
 
 // The seven centroid chains (Σw, Σw·p, Σw·q: icp.h:136-148) as sequential fp32 sums, computed on the integer grid of the
-// running sum's binade (rs_icp_estimate.hip: "grid chains").  Segments of 64 source points (original order), blocks of 64 segments.
+// running sum's binade (rs_icp_chain.hip: "grid chains").  Segments of 64 source points (original order), blocks of 64 segments.
 constexpr int CH_ROWS = 7, CH_SEG = 64, CH_BLK = 64;
 constexpr int REC_F4 = 3;        // float4 per correspondence record
 struct ChainRec { int e_sign; int lo[3], hi[3], D[3]; };   // exponent guess | sign << 8; per exponent e-1, e, e+1: the start mantissas it holds for and the advance
@@ -181,7 +181,7 @@ void launch_icp_corr( const IcpLaunch& L, hipStream_t st );     // phase A, phas
 void launch_icp_moments( const IcpLaunch& L, hipStream_t st );  // weights + moments (+ solve and loop-state update if L.solve)
 constexpr int FAITH_REC = 11;   // per correspondence: dist² (< 0: none), dot | weight, p, q, n
 void launch_icp_faithful( const IcpLaunch& L, hipStream_t st ); // the same step with the reference's own accumulation order and precisions
-// ... and the same bits computed in parallel (rs_icp_estimate.hip: "replay"): per problem and accumulator row (ICP_NMOM rows per pass)
+// ... and the same bits computed in parallel (rs_icp_faithful.hip: "replay"): per problem and accumulator row (ICP_NMOM rows per pass)
 struct ReplaySeg;
 struct ReplayBufs
 {

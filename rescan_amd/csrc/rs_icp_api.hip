@@ -195,7 +195,7 @@ inline int icp_plain_iterations( int n_source, int max_iter, bool fixed_iters )
 // PLAIN iterations without records (round 10).  A plain step is a sum in no particular order: nothing in it needs the 48-byte record a
 // search scatters to every source point's ORIGINAL index for the chains (icp_emit: pose and source reload, two gathers, three 16-byte
 // stores — 78 MB written per 1 M-point search, read back by k_chain_moments).  The search of a plain iteration therefore runs with
-// L.rec == null and k_plain_moments forms the moments from m_slot / m_d2 / m_dot in tile order (rs_icp_estimate.hip); the iterations that
+// L.rec == null and k_plain_moments forms the moments from m_slot / m_d2 / m_dot in tile order (rs_icp_chain.hip); the iterations that
 // keep the chains, or the RECORDS estimator's own, get their records from their own search as before.  RS_HIP_PLAIN_RECORDS=1 /
 // rs_hip_icp_plain_from_records( 1 ): the plain step from records again (A/B runs, tests).
 
@@ -941,7 +941,7 @@ int rs_hip_icp_align_batch( const rs_hip_cloud_t* source, const rs_hip_cloud_t* 
                             int32_t max_iter, int32_t fixed_iters, float* errs, int32_t* iters )
 {
   // Scan-sized sources: the reference's centroid sums by the grid chains — which give a problem up when a sum keeps changing
-  // binade (coordinates that straddle the origin in a cancelling order: rs_icp_estimate.hip, chain_walk_row); the batch is then run
+  // binade (coordinates that straddle the origin in a cancelling order: rs_icp_chain.hip, chain_walk_row); the batch is then run
   // again with those sums by pass 2 of the replay: the same bits, 0.9 ms per iteration at a million points instead of 0.09.
   // The estimators of large sources keep per-point records per problem (48 B with the chains, 44 B + the replay's rows when they
   // give up): many start poses of a whole scan are run in slices of problems whose records stay below RS_HIP_ICP_BATCH_BYTES

@@ -1,4 +1,6 @@
-// Diagnostics of the two kernels that end a plain ICP iteration (k_plain_moments, k_icp_update_wide; rs_icp_estimate.hip, its only includer).
+// Diagnostics of the two kernels that end a plain ICP iteration (k_plain_moments: rs_icp_chain.hip, k_icp_update_wide: rs_icp_update.hip).
+// Every estimator unit sees the macros (through rs_icp_estimate.h); a kernel's stamps live in its own unit's code object, so the unit that
+// defines RS_TAIL_DBG_MOM holds k_plain_moments' and hands them out, the one that defines RS_TAIL_DBG_UPD holds the others and the dump.
 // Build: tools/variant.sh taildbg -DRS_TAIL_DBG=1, load with RS_HIP_LIB=.../librescan_hip_taildbg.so, run an ICP call, then call
 //   extern "C" int rs_hip_debug_tail_dump( int n_iters );      (ctypes: declared nowhere else — it exists in that build only)
 // profiles/r11/iteration_tail_breakdown.txt is its output, condensed.
@@ -15,13 +17,20 @@
 #include <vector>
 namespace rs {
 constexpr int TD_ITERS = 16, TD_UPD = 8, TD_WAVES = 2048, TD_MOM = 16, TD_TILES = 11;
+hipError_t td_read_mom( unsigned long long* out );
+#ifdef RS_TAIL_DBG_UPD
 __device__ unsigned long long d_upd_dbg[TD_ITERS][ICP_NMOM][TD_UPD];   // [iteration][workgroup][phase]
+#endif
+#ifdef RS_TAIL_DBG_MOM
 __device__ unsigned long long d_mom_dbg[TD_ITERS][TD_WAVES][TD_MOM];   // [iteration][wave]{ start, loop entered, after tile 0.., [13] loop left, [14] end, [15] tiles }
+hipError_t td_read_mom( unsigned long long* out ) { return hipMemcpyFromSymbol( out, HIP_SYMBOL( d_mom_dbg ), sizeof( d_mom_dbg ) ); }
+#endif
 #define TD_STAMP( p, s ) do { if( p ) { __builtin_amdgcn_sched_barrier( 0 ); ( p )[s] = wall_clock64(); __builtin_amdgcn_sched_barrier( 0 ); } } while( 0 )
 // ... after everything the thread has loaded so far has arrived
 #define TD_STAMP_LOADED( p, s ) do { if( p ) { __atomic_signal_fence( __ATOMIC_SEQ_CST ); __builtin_amdgcn_s_waitcnt( 0x0F70 ); TD_STAMP( p, s ); } } while( 0 )
 } // namespace rs
 
+#ifdef RS_TAIL_DBG_UPD
 // (diagnostic build only) The stamps of the last call, as a table on stdout: per iteration, k_plain_moments per wave and k_icp_update_wide
 // per workgroup; times in microseconds (wall_clock64 ticks of 10 ns).
 extern "C" int rs_hip_debug_tail_dump( int n_iters )
@@ -30,7 +39,7 @@ extern "C" int rs_hip_debug_tail_dump( int n_iters )
   typedef unsigned long long u64;
   std::vector<u64> U( (size_t)TD_ITERS * ICP_NMOM * TD_UPD ), M( (size_t)TD_ITERS * TD_WAVES * TD_MOM );
   if( hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol( U.data(), HIP_SYMBOL( d_upd_dbg ), U.size() * 8 ) != hipSuccess ||
-      hipMemcpyFromSymbol( M.data(), HIP_SYMBOL( d_mom_dbg ), M.size() * 8 ) != hipSuccess ) return -1;
+      td_read_mom( M.data() ) != hipSuccess ) return -1;
   auto stats = []( std::vector<double>& v, double& lo, double& med, double& hi, double& mean )
   { lo = med = hi = mean = 0.0; if( v.empty() ) return; std::sort( v.begin(), v.end() ); lo = v.front(); hi = v.back(); med = v[v.size() / 2]; for( double x : v ) mean += x; mean /= (double)v.size(); };
   for( int it = 0; it < std::min( n_iters, TD_ITERS ); ++it )
@@ -88,6 +97,7 @@ extern "C" int rs_hip_debug_tail_dump( int n_iters )
   fflush( stdout );
   return 0;
 }
+#endif
 #else
 #define TD_STAMP( p, s ) do { } while( 0 )
 #define TD_STAMP_LOADED( p, s ) do { } while( 0 )

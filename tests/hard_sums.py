@@ -1,7 +1,7 @@
 """Seeded addend streams on which a parallel restatement of a sequential fp32 sum is easy to get subtly wrong, and the sequential
 reference to hold the ICP estimators' sums to.  A plain helper module like hard_clouds.py: no fixtures, no pytest hooks.
 
-The estimators of rescan_amd/csrc/rs_icp_estimate.hip reproduce the reference's seven centroid chains Σw, Σw·p, Σw·q (icp.h:136-148)
+The estimators of rescan_amd/csrc/rs_icp_faithful.hip and rs_icp_chain.hip reproduce the reference's seven centroid chains Σw, Σw·p, Σw·q (icp.h:136-148)
 — and the replay also the 33 fp32 + 2 fp64 accumulators of the normal equations — by parallel code that leans on what an fp32
 addition does inside one binade.  The cases that decide whether such code is right:
 

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — an fp64 restatement of ONE step of the device's ICP estimators (lib/rs/icp.h:210-298,393-402 as
-rescan_amd/csrc/rs_icp_estimate.hip and rs_math.h:icp_solve compute it), for the per-iteration checks of
+rescan_amd/csrc/rs_icp_update.hip, rs_icp_faithful.hip, rs_icp_chain.hip and rs_math.h:icp_solve compute it), for the per-iteration checks of
 tests/test_gpu_icp_steps.py and their CPU tests.  A plain helper module: no fixtures, no pytest hooks.
 
 Given the pose T_i a traced call reports before iteration i and that iteration's max_dist, `restate_step` returns the
@@ -8,7 +8,7 @@ pose after it and its error, by the estimator kind the device says it ran (resca
 * reference order / replay: the oracle's own icp_estimate_pt2pl on the oracle's correspondences (bit-identical expected);
 * lane / grid chains, the chains' sums from records: the reference's SEQUENTIAL fp32 centroid chains (icp.h:136-148,
   `1.0f / s` multiplied in, msh_vec_math.h:754) — the device's 2.5 sigma cut is taken from the searches' dist² statistics
-  (rs_icp_estimate.hip: chain_stats), modelled here from the same fp64 sums (`device_cut`);
+  (rs_icp_estimate.h: chain_stats), modelled here from the same fp64 sums (`device_cut`);
 * plain / k_icp_moments: fp64 centroids rounded to float as icp_solve rounds them, with the same cut;
 
 and for all four the centred normal equations  Σw c cᵀ, Σw c nᵀ, Σw n nᵀ, Σw c s, Σw n s, Σw s²  in fp64 straight from the fp32

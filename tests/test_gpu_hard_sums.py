@@ -288,20 +288,20 @@ def test_zz_nonfinite_streams_end_with_the_oracles_classes():
     overflows), through k_icp_faithful and the replay at n = 257, 4 097 and 16 385: every entry of the pose and the error is non-finite
     of the oracle's class (NaN, +inf, -inf) or equal to it in bits.
 
-    Why every loop of those routes ends whatever the values are (rescan_amd/csrc/rs_icp_estimate.hip) — all of them are counted loops
+    Why every loop of those routes ends whatever the values are (rescan_amd/csrc/rs_icp_faithful.hip) — all of them are counted loops
     over chunks, segments and addends; no exit rests on a comparison of summed values, which a NaN would make false for ever:
-      k_icp_faithful     faith_pass steps k0 = 0 .. n_chunks by FAITH_AHEAD (:555), n_chunks from n alone (:541); a chain wave adds a
-                         chunk by two fully unrolled loops over FAITH_CHUNK / 16 groups (:492, :513); the guess of sigma strides
-                         i < n (:628); the comparisons on sums (cnt == 0 :646, total <= 1e-7 :668, the band test :656) select a
+      k_icp_faithful     faith_pass steps k0 = 0 .. n_chunks by FAITH_AHEAD (:250), n_chunks from n alone (:236); a chain wave adds a
+                         chunk by two fully unrolled loops over FAITH_CHUNK / 16 groups (:187, :208); the guess of sigma strides
+                         i < n (:323); the comparisons on sums (cnt == 0 :341, total <= 1e-7 :363, the band test :351) select a
                          straight-line branch each — with a NaN total the pass goes on to the normal equations and the counted
                          6x6 solve;
-      k_replay_run       replay_terms strides t < REPLAY_SEG (:808); replay_run_chain adds t = 0 .. REPLAY_SEG - 1 (:952) — a NaN or
-                         infinite guess or value only clears `valid` (:944, :958), which keeps the shifts defined (:959) and marks
-                         the record unusable (:972);
-      k_replay_walk      replay_walk_row walks s0 < n_super (:1168), js < n_sup (:1173), j < n_here (:1180) and re-adds a segment by
-                         t4 < REPLAY_SEG / 4 (:1191); an unusable record costs one re-added segment, never a retry;
-      between them       k_replay_sums (:876), k_replay_scan (:897, :900, :908) and replay_compose_chain (s < n, :1023) are
-                         counted as well, and replay_params' tests (:757-:777) only choose whether a pass runs at all.
+      k_replay_run       replay_terms strides t < REPLAY_SEG (:503); replay_run_chain adds t = 0 .. REPLAY_SEG - 1 (:647) — a NaN or
+                         infinite guess or value only clears `valid` (:639, :653), which keeps the shifts defined (:654) and marks
+                         the record unusable (:667);
+      k_replay_walk      replay_walk_row walks s0 < n_super (:848), js < n_sup (:853), j < n_here (:860) and re-adds a segment by
+                         t4 < REPLAY_SEG / 4 (:871); an unusable record costs one re-added segment, never a retry;
+      between them       k_replay_sums (:571), k_replay_scan (:592, :595, :603) and replay_compose_chain (s < n, :718) are
+                         counted as well, and replay_params' tests (:452-:472) only choose whether a pass runs at all.
     Nothing had to be changed for this test."""
     run_child(r"""
 checked = 0

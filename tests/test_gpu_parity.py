@@ -474,7 +474,7 @@ def test_exact_centroid_chains_are_the_sequential_sums(capi, gscene, scene_cloud
 
 def test_lane_chains_are_the_sequential_sums(capi, gscene, scene_clouds):
     """Round 6: object-sized sources above the reference-order threshold take the LANE chains (one wave per centroid chain, 1 024 addends
-    per stretch, sixteen per lane, on the integer grid of the sum's binade, fp32 one by one where that does not hold: rs_icp_estimate.hip).  The seven sums
+    per stretch, sixteen per lane, on the integer grid of the sum's binade, fp32 one by one where that does not hold: rs_icp_chain.hip).  The seven sums
     must be the sequential fp32 sums whatever the input: whole icp_align runs against the same estimator with the sums by pass 2 of
     the replay (itself held against the sequential kernel) — poses, errors and iteration counts bit for bit — on every object
     fixture, batches, a scan whose x coordinates straddle zero (a chain that changes sign), a scan that begins with unmatched points

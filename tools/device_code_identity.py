@@ -39,7 +39,7 @@ def per_symbol(dis):
             line = "%s// +%x:%s" % (m.group(1), int(m.group(2), 16) - base, m.group(3))
         out[name].append(line)
     for v in out.values():      # what fills the gap up to the next symbol, or the end of the section, is not the kernel's
-        while v and v[-1].split("//")[0].strip() in ("s_nop 0", "s_code_end"):
+        while v and v[-1].split("//")[0].strip() in ("s_nop 0", "s_code_end", "..."):      # ("...": llvm-objdump's line for a run of zeros)
             v.pop()
     return {k: "\n".join(v) for k, v in out.items()}
 

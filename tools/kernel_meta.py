@@ -2,7 +2,7 @@
 import os, re, subprocess, sys, tempfile
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = sys.argv[1] if len(sys.argv) > 1 else ""
-for tu in ("rs_icp_search", "rs_icp_estimate", "rs_score", "rs_rows", "rs_isect", "rs_arrange", "rs_mesh", "rs_planes", "rs_split", "rs_propose"):
+for tu in ("rs_icp_search", "rs_icp_update", "rs_icp_faithful", "rs_icp_chain", "rs_score", "rs_rows", "rs_isect", "rs_arrange", "rs_mesh", "rs_planes", "rs_split", "rs_propose"):
     d = tempfile.mkdtemp(prefix="kmeta")
     subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-slp-vectorize", "-c", "--save-temps",
                     os.path.join(root, "rescan_amd/csrc/%s.hip" % tu), "-o", "x.o"], cwd=d, check=True, stderr=subprocess.DEVNULL)
