@@ -25,8 +25,10 @@ RS_HD inline Mat4 mat4_identity() { Mat4 r; for( int i = 0; i < 16; ++i ) r.m[i]
 // (it differs from (float)sin((double)x) for 0.85 % of the arguments), and the reference's poses carry exactly these
 // bits (msh_rotate, msh_vec_math.h:2091-2092).  The fused steps are the ones of libm's FMA build, which every x86-64
 // host of the last decade selects; pinned against the host's sinf/cosf on 6e8 arguments with zero mismatches
-// (tests/test_capi_cpu.py checks a sample on every run).  |x| >= 120, inf and NaN (never an ICP step) fall back to
-// the double-precision function rounded once.
+// (tests/test_capi_cpu.py checks a sample on every run).  |x| >= 120 IS an ICP step: a segment with one normal (a floor, a
+// wall) whose normals carry rounding noise gives the unpivoted solve pivots of either sign near zero and steps of hundreds to
+// tens of thousands of radians (tests/hard_systems.py: tilted_jitter), so that range takes libm's third branch as well, the
+// mantissa times a window of 2/π, and is pinned to the host's bits up to FLT_MAX by the same test.  Inf and NaN give NaN.
 RS_HD inline float rs_sincosf_poly( double x, double x2, bool cosine, bool negate_cos )
 {
   // __sincosf_table[0]; table[1] is the same with c0..c4 negated
@@ -66,7 +68,27 @@ RS_HD inline void rs_sincosf_model( float a, float& s, float& c )
     c = rs_sincosf_poly( xs, x2, ( ( n ^ 1 ) & 1 ) != 0, tab1 );
     return;
   }
-  s = (float)sin( x ); c = (float)cos( x );
+  if( top12 >= 0x7f8 ) { s = c = a - a; return; }  // inf, NaN: NaN (libm's __math_invalidf)
+  // |a| >= 120: reduce_large — the 24-bit mantissa, shifted by the low three exponent bits, times the 96-bit window of 2/π that
+  // the upper exponent bits select; bits 62 and up of the product are the quadrant, the rest is the reduced argument in units
+  // of 2^-62 quarter turns.  W[i] = floor( 2/π · 2^(8 (i + 1)) ) mod 2^32 (tests/test_capi_cpu.py computes the words again
+  // with integer arithmetic and reads them back out of this file).
+  const uint32_t W[24] = { 0xa2u, 0xa2f9u, 0xa2f983u, 0xa2f9836eu, 0xf9836e4eu, 0x836e4e44u, 0x6e4e4415u, 0x4e441529u,
+                           0x441529fcu, 0x1529fc27u, 0x29fc2757u, 0xfc2757d1u, 0x2757d1f5u, 0x57d1f534u, 0xd1f534ddu, 0xf534ddc0u,
+                           0x34ddc0dbu, 0xddc0db62u, 0xc0db6295u, 0xdb629599u, 0x6295993cu, 0x95993c43u, 0x993c4390u, 0x3c439041u };
+  const uint32_t* w = W + ( ( u >> 26 ) & 15 );
+  const uint32_t m = ( ( u & 0xffffffu ) | 0x800000u ) << ( ( u >> 23 ) & 7 );
+  const uint64_t hi = (uint64_t)( m * w[0] ) << 32, mid = (uint64_t)m * w[4], lo = (uint64_t)m * w[8];
+  uint64_t r = ( ( lo >> 32 ) | hi ) + mid;
+  const uint64_t q = ( r + ( 1ull << 61 ) ) >> 62;
+  r -= q << 62;
+  const double xr = (double)(int64_t)r * 0x1.921FB54442D18p-62;
+  const int n = (int)q + (int)( u >> 31 );          // sin is odd, cos even: the sign of a moves the quadrant
+  const double sign = ( ( n & 3 ) == 1 || ( n & 3 ) == 2 ) ? -1.0 : 1.0;
+  const double xs = xr * sign, x2 = xr * xr;
+  const bool tab1 = ( n & 2 ) != 0;
+  s = rs_sincosf_poly( xs, x2, ( q & 1 ) != 0, tab1 );
+  c = rs_sincosf_poly( xs, x2, ( ( q ^ 1 ) & 1 ) != 0, tab1 );
 }
 
 // cosf/sinf of the host libm — by definition what the reference calls; on the device the model above.

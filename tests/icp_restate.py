@@ -215,12 +215,12 @@ def restate_step(oracle, kind, corrs, T1):
         return T1.copy(), None, info
     if kind in REF_KINDS:
         tw = np.add.accumulate(corrs.w_ref, dtype=np.float32)[-1]
-        if tw <= f32(1e-7):
+        if float(tw) <= 1e-7:                                      # icp.h:466: the float against the DOUBLE 1e-7; f32(1e-7) lies above it
             return T1.copy(), None, info
         err, T = oracle.icp_estimate_pt2pl(corrs.p1, corrs.p2, corrs.n2, corrs.w_ref, T1)
         return T, f32(err), info
     w, info["ambiguous"] = device_weights(corrs.d2, corrs.w_uncut, corrs.max_dist)
-    if f32(np.sum(w.astype(np.float64))) <= f32(1e-7):         # icp_solve: (float)W <= 1e-7
+    if float(f32(np.sum(w.astype(np.float64)))) <= 1e-7:       # icp_solve: (float)W <= 1e-7, compared in double
         return T1.copy(), None, info
     if kind in CHAIN_KINDS:
         c1, c2, _ = seq_centroids(corrs.p1, corrs.p2, w)

@@ -76,7 +76,10 @@ def test_device_sincosf_model_is_the_host_libm(lib):
     """The reference composes its poses with libm's sinf/cosf (msh_vec_math.h:2091-2092), which are not correctly
     rounded (0.85 % of the arguments differ from the rounded double result); the ICP loop runs on the device, so the
     device carries a restatement of glibc's algorithm.  It must return libm's bits: ICP-step-sized angles, the whole
-    polynomial range, the range-reduced one, and the edges of each."""
+    polynomial range, the range-reduced one, the large-argument one (|x| >= 120, which a one-normal segment's step reaches:
+    tests/hard_systems.py) log-uniformly up to FLT_MAX and uniformly up to 1e4, and the edges of each: 120 itself, both sides of
+    every power of two above it, FLT_MAX.  Inf and NaN give NaN.  (A stand-alone host build of the model had zero mismatches on
+    3.7e7 arguments of that range, every 37th float from 120 to FLT_MAX among them.)"""
     import ctypes as C
     from rescan_amd import capi
     libm = C.CDLL("libm.so.6")
@@ -88,18 +91,48 @@ def test_device_sincosf_model_is_the_host_libm(lib):
         10.0 ** rng.uniform(-7, -2, 20000) * rng.choice([-1, 1], 20000),
         np.array([0.0, -0.0, 2.0 ** -12, np.nextafter(np.float32(2.0 ** -12), np.float32(0)), 0.75, np.nextafter(np.float32(0.75), np.float32(0)),
                   np.pi / 4, np.pi / 2, np.pi, 119.99999, 120.0, 1e5, -1e5]),
+        np.exp(rng.uniform(np.log(120.0), np.log(3.4e38), 60000)) * rng.choice([-1, 1], 60000), rng.uniform(120, 1e4, 20000),
     ]).astype(np.float32)
+    edges = np.ldexp(np.float32(1), np.arange(7, 128)).astype(np.float32).view(np.uint32)[:, None].astype(np.int64) + np.arange(-2, 3)
+    edges = edges[edges < 0x7f800000].astype(np.uint32)
+    fmax = np.finfo(np.float32).max
+    x = np.concatenate([x, edges.ravel().view(np.float32), -edges.ravel().view(np.float32),
+                        np.array([120.0, -120.0, np.nextafter(np.float32(120), np.float32(121)), fmax, -fmax], np.float32)])
     s, c = capi.sincosf_model(x)
     want_s = np.array([libm.sinf(float(v)) for v in x], np.float32)
     want_c = np.array([libm.cosf(float(v)) for v in x], np.float32)
-    # (beyond |x| = 120 the model rounds the double-precision function once: equal to libm's third branch
-    #  except in its rare misroundings — not an ICP step, not asserted bit for bit)
-    small = np.abs(x) < 120
-    assert (s[small].view(np.uint32) == want_s[small].view(np.uint32)).all()
-    assert (c[small].view(np.uint32) == want_c[small].view(np.uint32)).all()
-    assert np.abs(s[~small] - want_s[~small]).max() < 1e-6 and np.abs(c[~small] - want_c[~small]).max() < 1e-6
+    assert (s.view(np.uint32) == want_s.view(np.uint32)).all(), x[s.view(np.uint32) != want_s.view(np.uint32)][:8]
+    assert (c.view(np.uint32) == want_c.view(np.uint32)).all(), x[c.view(np.uint32) != want_c.view(np.uint32)][:8]
+    assert (np.abs(x) >= 120).sum() > 80000
+    s, c = capi.sincosf_model(np.array([np.inf, -np.inf, np.nan], np.float32))
+    assert np.isnan(s).all() and np.isnan(c).all()
     # the point of the exercise: libm is NOT the correctly rounded function
     assert (want_s != np.sin(x.astype(np.float64)).astype(np.float32)).sum() > 100
+
+
+def test_two_over_pi_words_are_what_integer_arithmetic_gives():
+    """The 24 words of 2/pi that rs_sincosf_model's large-argument reduction reads (rescan_amd/csrc/rs_math.h), computed again:
+    pi from Machin's formula in integers with 64 guard bits, 2/pi by one integer division to 400 bits, word i =
+    floor(2/pi * 2^(8 (i + 1))) mod 2^32.  The computation is itself checked: its leading 53 bits are the double 2 / math.pi."""
+    import math
+
+    def atan_inv(q, bits):                       # atan(1 / q) * 2^bits
+        t = (1 << bits) // q
+        s, k = t, 1
+        while t:
+            t //= q * q
+            k += 2
+            s += -(t // k) if (k // 2) % 2 else t // k
+        return s
+    B = 400
+    pi = (16 * atan_inv(5, B + 64) - 4 * atan_inv(239, B + 64)) >> 64
+    two_over_pi = (2 << (2 * B)) // pi
+    assert abs((two_over_pi >> (B - 60)) / 2.0 ** 60 - 2 / math.pi) < 2.0 ** -52
+    assert abs(pi / 2.0 ** B - math.pi) < 2.0 ** -50
+    words = [(two_over_pi >> (B - 8 * (i + 1))) & 0xffffffff for i in range(24)]
+    src = open(os.path.join(ROOT, "rescan_amd", "csrc", "rs_math.h")).read()
+    body = re.search(r"const uint32_t W\[24\] = \{(.*?)\};", src, flags=re.S).group(1)
+    assert [int(w.rstrip("u"), 16) for w in re.findall(r"0x[0-9a-f]+u", body)] == words
 
 
 def test_fails_loudly_without_gpu(lib):

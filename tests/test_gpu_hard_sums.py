@@ -67,7 +67,8 @@ ROUTES = {"ref_order": dict(icp_reference_order_below=BIG),
           "moments": dict(icp_reference_order_below=0, icp_lane_chains_below=0, icp_replay_below=0, icp_exact_centroids=0)}
 def vanishing(w):
     # the weights' sequential fp32 sum is <= 1e-7 (icp.h:466-470: icp_align keeps the pose; include/rescan_hip.h: so does the estimate)
-    return bool(H.seq(w)[-1] <= 1e-7)
+    # (compared in DOUBLE as the reference and the library do: a sum of exactly f32(1e-7) = 1.0000000116860974e-07 has not vanished)
+    return bool(float(H.seq(w)[-1]) <= 1e-7)
 def reference_estimate(p1, p2, n2, w, T1):
     if vanishing(w):
         return F(0.0), np.asarray(T1, F).copy()
