@@ -178,6 +178,26 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
                            rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
                            int32_t** out_class, int32_t** out_instance, rsd_mat4_t* xform );
 
+/* rsd_augment_model for all placements of an arrangement in one device call (rs_hip_cloud_fuse_arrangement): the scan's ids go to
+ * the device once and are cut once, and every round of placements shares one permutation pass and one merge launch.  The scan's
+ * arrays as above; per placement p: the model's six arrays (entries of arrays of n_placements pointers) with n_model[p], the pose,
+ * uidx and is_static, and model_from[p]: -1, or the index q < p of an earlier placement whose resulting shape is p's model — its
+ * merged arrays, or q's own model when no scan point carries q's uidx — which is what the reference's loop sees when the same
+ * object is placed twice or a novel object copies a shape an earlier placement replaced (database_update.cpp:40-56, :89); p's own
+ * model arrays are then ignored and may be NULL.  Outputs: arrays of n_placements pointers, entry p malloc'ed as rsd_augment_model
+ * allocates it (every instance id uidx[p]) or NULL with out_n[p] = 0 when no scan point carries uidx[p]; xforms (may be NULL): one
+ * per placement.  Returns 0, or a negative RS_HIP_E_* code with nothing allocated.  Placement by placement the arrays are those of
+ * rsd_augment_model given the same model. */
+int32_t rsd_augment_models( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_nor, const rsd_vec3_t* scan_col, const float* scan_radii,
+                            const float* scan_qual, const int32_t* scan_class, const int32_t* scan_instance, int32_t n_scan,
+                            int32_t n_placements,
+                            const rsd_vec3_t* const* model_pos, const rsd_vec3_t* const* model_nor, const rsd_vec3_t* const* model_col,
+                            const float* const* model_radii, const float* const* model_qual, const int32_t* const* model_class,
+                            const int32_t* n_model, const int32_t* model_from,
+                            const rsd_mat4_t* poses, const int32_t* uidx, const int32_t* is_static,
+                            rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
+                            int32_t** out_class, int32_t** out_instance, int64_t* out_n, rsd_mat4_t* xforms );
+
 /* The loop of seg2rsdb's pointcloud_to_rsdb (apps/seg2rsdb/main.cpp:80-136) on pointcloud's level-0 arrays: the instances in order
  * of first appearance, every instance's points cut out in input order and, unless the class of its first point is among
  * static_classes (the caller's rsdb_is_class_static, which needs the class table), moved by msh_translate( identity, -centroid ) with

@@ -560,10 +560,75 @@ rs_hip_cloud_t* rs_hip_cloud_create_fused( const rs_hip_cloud_t* scan, const int
                                            float xform_out[16], float* icp_err, int32_t* source, int32_t* scan_index,
                                            int64_t* n_extracted );
 
-/* Diagnostics: where rs_hip_cloud_create_fused's time went on the calling thread since the last call of this function —
- * extraction | ICP | permutation | merge | index build, seconds (out may be NULL) — and whether the next calls keep the
- * clock (enable != 0: they then synchronise after every stage). */
+/* Diagnostics: where the time of rs_hip_cloud_create_fused / rs_hip_cloud_fuse_arrangement went on the calling thread since
+ * the last call of this function — extraction | ICP | permutation | merge | index build, seconds (out may be NULL) — and
+ * whether the next calls keep the clock (enable != 0: they then synchronise after every stage). */
 void rs_hip_fuse_seconds( double out[5], int32_t enable );
+
+/* ---- the whole arrangement in one call -------------------------------------------------------- */
+
+/* The permutations of n_placements independent shuffles, concatenated: perm[off_p + i] (off_p = n[0] + .. + n[p - 1]) is
+ * rs_hip_shuffle_permutation( n[p], seed )[i], a LOCAL index.  Every placement restarts the generator at `seed`
+ * (rs_pointcloud_merge seeds it itself).  One draw, one sort and one walk for all of them.  A size may be 0 or 1.
+ * RS_HIP_E_ARG: a negative count, NULL arrays; RS_HIP_E_CAPACITY: an n[p] above 2^24, or a sum above 2^31 - 2. */
+int rs_hip_shuffle_permutations( const int64_t* n, int32_t n_placements, uint32_t seed, int32_t* perm );
+
+/* rs_hip_merge_shuffled for n_placements placements in one permutation pass and one merge launch.  a_pos / a_nor / b_pos /
+ * b_nor: n_placements host pointers each (an entry may be NULL where its count is 0); xforms: 16 floats per placement;
+ * out_pos / out_nor / source (may be NULL): the placements' results one after the other, placement p's at element
+ * sum( n_a[q] + n_b[q], q < p ); source is local to its placement, as rs_hip_merge_shuffled returns it.  Refuses what
+ * rs_hip_merge_shuffled and rs_hip_shuffle_permutations refuse. */
+int rs_hip_merge_shuffled_multi( int32_t n_placements, const float* const* a_pos, const float* const* a_nor, const int64_t* n_a,
+                                 const float* xforms, const float* const* b_pos, const float* const* b_nor, const int64_t* n_b,
+                                 uint32_t seed, float* out_pos, float* out_nor, int32_t* source /* may be NULL */ );
+
+/* One placement of an arrangement.  model_from names the model:
+ *   -1            `model`, the object's level-0 cloud
+ *   q, 0 <= q < p the shape placement q of the same call leaves: its merged cloud, or — when no scan point carries q's uidx
+ *                 and the object stays as it is (database_update.cpp:58) — q's own model, resolved the same way.  This is the
+ *                 reference's loop where the same object_idx is placed twice, or where a novel object copies a shape an
+ *                 earlier placement already replaced (:51 after :89).  `model` is ignored. */
+typedef struct rs_hip_fuse_placement {
+  int32_t uidx;                 /* the placement's instance id */
+  int32_t refine;               /* 0 for a static object */
+  int32_t model_from;
+  int32_t reserved;
+  const rs_hip_cloud_t* model;
+  float pose[16];
+} rs_hip_fuse_placement_t;
+
+/* What rs_hip_cloud_create_fused returns for the placement alone, given the same model.  source and scan_index are the
+ * caller's arrays (each may be NULL): source has room for n_extracted + the model's size entries (the scan's size + the
+ * model's always suffices; a dependent placement's model is as large as what its model_from left), scan_index for the
+ * scan's size.  The call writes the other fields: cloud is NULL and n_extracted 0 where no scan point carries uidx (xform
+ * and icp_err are then 0).  The caller destroys every cloud. */
+typedef struct rs_hip_fuse_result {
+  rs_hip_cloud_t* cloud;
+  int64_t n_extracted;
+  float xform[16];
+  float icp_err;
+  int32_t reserved;
+  int32_t* source;
+  int32_t* scan_index;
+} rs_hip_fuse_result_t;
+
+/* rsdu_augment_database's loop over all placements of an arrangement (database_update.cpp:28-91) without the points leaving
+ * the device: the scan's instance ids are uploaded once and cut by the split's table and stable partition (segment k of its
+ * order is what rs_hip_select_by_ids returns for that id); the placements run in rounds by the depth of their model_from
+ * chains (an ordinary arrangement is one round); a round runs one rs_hip_icp_align per dynamic placement, then ONE
+ * permutation pass and ONE merge launch for all its placements, then one index build per merged cloud.  Two placements with
+ * the same uidx extract the same points.  Every result is bit for bit rs_hip_cloud_create_fused's for that placement alone
+ * wherever that call is bit for bit the reference; above 16 384 extracted points xform is within the ICP's 1e-4 bar and
+ * the merged arrays are bit for bit the merge under the xform returned.
+ * Refusals, decided on the host before any fuse kernel is launched, results untouched: RS_HIP_E_ARG for a negative
+ * n_placements, NULL scan / placements / results / ids, a model_from outside [-1, p), model_from == -1 without a model, a
+ * cloud without normals; RS_HIP_E_CAPACITY for more than 4096 distinct instance ids (the split's table finds that; there is
+ * no fallback walk), more than 2^24 merged points in one placement, more than 2^31 - 2 merged points in one round.
+ * n_placements == 0 succeeds.  A failure part of the way destroys the clouds already made and writes no result record
+ * (the contents of source / scan_index arrays are then unspecified). */
+int rs_hip_cloud_fuse_arrangement( const rs_hip_cloud_t* scan, const int32_t* scan_instance_ids,
+                                   const rs_hip_fuse_placement_t* placements, int32_t n_placements,
+                                   float max_dist, float max_angle, float cell_size, rs_hip_fuse_result_t* results );
 
 /* ---- scan to object models: the row that opens a sequence ----------------- */
 

@@ -127,6 +127,10 @@ SIGNATURES = {
     "rs_hip_cloud_create_fused": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                                C.c_float, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "rs_hip_fuse_seconds": (None, [C.c_void_p, C.c_int32]),
+    "rs_hip_shuffle_permutations": (C.c_int, [C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p]),
+    "rs_hip_merge_shuffled_multi": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rs_hip_cloud_fuse_arrangement": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "rs_hip_split_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "rs_hip_instance_table": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "rs_hip_split_by_instance": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
@@ -375,6 +379,52 @@ class Cloud:
         _check(lib.rs_hip_cloud_points(h, self._pos.ctypes.data, self._nor.ctypes.data))
         return self, info
 
+    @classmethod
+    def fuse_arrangement(cls, scan, scan_instance_ids, placements, max_dist=0.05, max_angle=np.float32(10.0 * 0.005555555556 * np.pi), cell_size=-1.0):
+        """rsdu_augment_database's loop over all placements of an arrangement in one call (rs_hip_cloud_fuse_arrangement).
+        placements: dicts with uidx, pose, and model (a Cloud) or model_from (the index of an earlier placement whose resulting
+        shape is the model; default -1: `model`); refine defaults to True.  Returns one (cloud, info) per placement, exactly what
+        Cloud.fused returns for it alone given the same model; (None, info) where no scan point carries the uidx."""
+        lib = load()
+        ids = np.ascontiguousarray(scan_instance_ids, np.int32).ravel()
+        if len(ids) != scan.n:
+            raise ValueError("scan_instance_ids: one entry per scan point")
+        P = len(placements)
+        recs = (FusePlacement * max(P, 1))(); outs = (FuseResult * max(P, 1))()
+        keep, sources, indices, n_model, n_shape, counts = [], [], [], [], [], {}
+        for p, pl in enumerate(placements):
+            frm = int(pl.get("model_from", -1)); model = pl.get("model")
+            pose = _f32(pl["pose"]).ravel()
+            recs[p].uidx = int(pl["uidx"]); recs[p].refine = int(bool(pl.get("refine", True))); recs[p].model_from = frm
+            recs[p].model = model.handle if (frm == -1 and model is not None) else None
+            recs[p].pose[:] = pose.tolist()
+            keep.append(model)
+            # the sizes follow from the ids alone; they only size the arrays handed in (the library judges the arguments itself)
+            if recs[p].uidx not in counts:
+                counts[recs[p].uidx] = int(np.count_nonzero(ids == recs[p].uidx))
+            n_ext = counts[recs[p].uidx]
+            nm = (model.n if model is not None else 0) if not 0 <= frm < p else n_shape[frm]
+            n_model.append(nm); n_shape.append(n_ext + nm if n_ext else nm)
+            sources.append(np.zeros(max(n_ext + nm, 1), np.int32)); indices.append(np.zeros(max(n_ext, 1), np.int32))
+            outs[p].source = sources[p].ctypes.data; outs[p].scan_index = indices[p].ctypes.data
+        _check(lib.rs_hip_cloud_fuse_arrangement(scan.handle, ids.ctypes.data, C.addressof(recs), P, float(max_dist), float(max_angle), float(cell_size),
+                                                 C.addressof(outs)))
+        made = []
+        for p in range(P):
+            na = int(outs[p].n_extracted); h = outs[p].cloud
+            info = dict(xform=np.array(outs[p].xform[:], np.float32), icp_err=float(outs[p].icp_err), source=sources[p][:na + n_model[p] if h else 0].copy(),
+                        scan_index=indices[p][:na].copy(), n_extracted=na)
+            cloud = None
+            if h:
+                cloud = cls.__new__(cls)
+                cloud.handle = h; cloud.n = na + n_model[p]
+                cloud._pos = np.zeros((cloud.n, 3), np.float32); cloud._nor = np.zeros((cloud.n, 3), np.float32)
+            made.append((cloud, info))
+        for cloud, _ in made:
+            if cloud is not None:
+                _check(lib.rs_hip_cloud_points(cloud.handle, cloud._pos.ctypes.data, cloud._nor.ctypes.data))
+        return made
+
     def split_objects(self, class_ids, instance_ids, static_classes=(), cell_size=-1.0):
         """seg2rsdb's pointcloud_to_rsdb on this level-0 cloud with normals (rs_hip_cloud_split_objects): one indexed cloud per
         instance, in order of first appearance, the dynamic ones centred; the points never visit the host on the way.  Returns
@@ -546,6 +596,46 @@ def fuse_seconds(enable=True):
     out = np.zeros(5, np.float64)
     load().rs_hip_fuse_seconds(out.ctypes.data, int(bool(enable)))
     return out
+
+
+class FusePlacement(C.Structure):
+    """rs_hip_fuse_placement_t"""
+    _fields_ = [("uidx", C.c_int32), ("refine", C.c_int32), ("model_from", C.c_int32), ("reserved", C.c_int32), ("model", C.c_void_p), ("pose", C.c_float * 16)]
+
+
+class FuseResult(C.Structure):
+    """rs_hip_fuse_result_t"""
+    _fields_ = [("cloud", C.c_void_p), ("n_extracted", C.c_int64), ("xform", C.c_float * 16), ("icp_err", C.c_float), ("reserved", C.c_int32),
+                ("source", C.c_void_p), ("scan_index", C.c_void_p)]
+
+
+def shuffle_permutations(sizes, seed=SEED_MERGE):
+    """The permutations of len(sizes) independent shuffles in one device pass (rs_hip_shuffle_permutations), concatenated; each
+    slice holds local indices: the slice of placement p equals shuffle_plan(sizes[p], seed)."""
+    n = np.ascontiguousarray(sizes, np.int64).ravel()
+    perm = np.zeros(max(int(n.clip(min=0).sum()), 0) if len(n) else 0, np.int32)
+    _check(load().rs_hip_shuffle_permutations(n.ctypes.data if len(n) else None, len(n), int(seed), perm.ctypes.data if len(perm) else None))
+    return perm
+
+
+def merge_shuffled_multi(parts, seed=SEED_MERGE):
+    """merge_shuffled for every (a_pos, a_nor, xform, b_pos, b_nor) of parts in one permutation pass and one merge launch
+    (rs_hip_merge_shuffled_multi): a list of (pos, nor, source), one per part."""
+    P = len(parts)
+    arrays = [[_f32(x).reshape(-1, 3) for x in (a_pos, a_nor, b_pos, b_nor)] for a_pos, a_nor, _, b_pos, b_nor in parts]
+    for a_pos, a_nor, b_pos, b_nor in arrays:
+        if len(a_nor) != len(a_pos) or len(b_nor) != len(b_pos):
+            raise ValueError("one normal per point")
+    xforms = np.ascontiguousarray(np.stack([_f32(x[2]).ravel() for x in parts]) if P else np.zeros((0, 16)), np.float32)
+    n_a = np.array([len(a[0]) for a in arrays], np.int64); n_b = np.array([len(a[2]) for a in arrays], np.int64)
+    ptrs = [(C.c_void_p * max(P, 1))(*[a[k].ctypes.data if len(a[k]) else None for a in arrays]) for k in range(4)]
+    sizes = n_a + n_b; total = int(sizes.sum())
+    pos = np.zeros((total, 3), np.float32); nor = np.zeros((total, 3), np.float32); source = np.zeros(total, np.int32)
+    _check(load().rs_hip_merge_shuffled_multi(P, C.addressof(ptrs[0]), C.addressof(ptrs[1]), n_a.ctypes.data, xforms.ctypes.data, C.addressof(ptrs[2]),
+                                              C.addressof(ptrs[3]), n_b.ctypes.data, int(seed), pos.ctypes.data if total else None,
+                                              nor.ctypes.data if total else None, source.ctypes.data if total else None))
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    return [(pos[off[p]:off[p + 1]], nor[off[p]:off[p + 1]], source[off[p]:off[p + 1]]) for p in range(P)]
 
 
 class SplitOut(C.Structure):

@@ -957,6 +957,103 @@ int64_t rsd_augment_model( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_no
   return (int64_t)n;
 }
 
+int32_t rsd_augment_models( const rsd_vec3_t* scan_pos, const rsd_vec3_t* scan_nor, const rsd_vec3_t* scan_col, const float* scan_radii,
+                            const float* scan_qual, const int32_t* scan_class, const int32_t* scan_instance, int32_t n_scan,
+                            int32_t n_placements,
+                            const rsd_vec3_t* const* model_pos, const rsd_vec3_t* const* model_nor, const rsd_vec3_t* const* model_col,
+                            const float* const* model_radii, const float* const* model_qual, const int32_t* const* model_class,
+                            const int32_t* n_model, const int32_t* model_from,
+                            const rsd_mat4_t* poses, const int32_t* uidx, const int32_t* is_static,
+                            rsd_vec3_t** out_pos, rsd_vec3_t** out_nor, rsd_vec3_t** out_col, float** out_radii, float** out_qual,
+                            int32_t** out_class, int32_t** out_instance, int64_t* out_n, rsd_mat4_t* xforms )
+{
+  const int P = n_placements;
+  if( P < 0 ) { fprintf( stderr, "rescan_dropin: augment_models: a negative number of placements\n" ); return RS_HIP_E_ARG; }
+  if( P == 0 ) return 0;
+  if( !scan_pos || !scan_nor || !scan_col || !scan_radii || !scan_qual || !scan_class || !scan_instance || n_scan < 0 ||
+      !model_pos || !model_nor || !model_col || !model_radii || !model_qual || !model_class || !n_model || !model_from || !poses || !uidx || !is_static ||
+      !out_pos || !out_nor || !out_col || !out_radii || !out_qual || !out_class || !out_instance || !out_n )
+  { fprintf( stderr, "rescan_dropin: augment_models: null arrays or a negative count\n" ); return RS_HIP_E_ARG; }
+  for( int p = 0; p < P; ++p )
+  {
+    if( model_from[p] < -1 || model_from[p] >= p ) { fprintf( stderr, "rescan_dropin: augment_models: placement %d: model_from outside [-1, %d)\n", p, p ); return RS_HIP_E_ARG; }
+    if( model_from[p] == -1 && ( n_model[p] < 0 || ( n_model[p] > 0 && ( !model_pos[p] || !model_nor[p] || !model_col[p] || !model_radii[p] || !model_qual[p] || !model_class[p] ) ) ) )
+    { fprintf( stderr, "rescan_dropin: augment_models: placement %d: null model arrays or a negative count\n", p ); return RS_HIP_E_ARG; }
+  }
+  const CloudRef scan = cached_cloud( scan_pos, scan_nor, n_scan, -1.0f );
+  if( !scan ) return RS_HIP_E_RUNTIME;
+  std::vector<CloudRef> held;
+  std::vector<rs_hip_fuse_placement_t> recs( (size_t)P );
+  std::vector<rs_hip_fuse_result_t> res( (size_t)P );
+  // the shape every placement leaves, on the host: the attributes of a dependent placement's model are its predecessor's
+  struct Shape { const rsd_vec3_t* col; const float* radii; const float* qual; const int32_t* cls; int64_t n; };
+  std::vector<Shape> model( (size_t)P ), shape( (size_t)P );
+  std::vector<std::vector<int32_t>> source( (size_t)P ), scan_index( (size_t)P );
+  for( int p = 0; p < P; ++p )
+  {
+    rs_hip_fuse_placement_t& R = recs[(size_t)p];
+    R = rs_hip_fuse_placement_t{};
+    R.uidx = uidx[p]; R.refine = is_static[p] ? 0 : 1; R.model_from = model_from[p];
+    std::memcpy( R.pose, poses[p].data, 64 );
+    int64_t n_ext = 0;
+    for( int32_t i = 0; i < n_scan; ++i ) n_ext += scan_instance[i] == uidx[p] ? 1 : 0;
+    if( model_from[p] < 0 )
+    {
+      held.push_back( cached_cloud( model_pos[p], model_nor[p], n_model[p], -1.0f ) );
+      if( !held.back() ) return RS_HIP_E_RUNTIME;
+      R.model = held.back().get();
+      model[(size_t)p] = Shape{ model_col[p], model_radii[p], model_qual[p], model_class[p], n_model[p] };
+    }
+    else model[(size_t)p] = Shape{ nullptr, nullptr, nullptr, nullptr, shape[(size_t)model_from[p]].n };
+    shape[(size_t)p].n = n_ext > 0 ? n_ext + model[(size_t)p].n : model[(size_t)p].n;
+    source[(size_t)p].resize( (size_t)std::max<int64_t>( 1, n_ext + model[(size_t)p].n ) ); scan_index[(size_t)p].resize( (size_t)std::max<int64_t>( 1, n_ext ) );
+    res[(size_t)p] = rs_hip_fuse_result_t{};
+    res[(size_t)p].source = source[(size_t)p].data(); res[(size_t)p].scan_index = scan_index[(size_t)p].data();
+  }
+  const float max_angle = (float)( 10.0f * 0.005555555556 * 3.1415926535897932384626433832 );       // msh_deg2rad( 10.0f ), msh_std.h:618,625
+  const int rc = rs_hip_cloud_fuse_arrangement( scan.get(), scan_instance, recs.data(), P, 0.05f, max_angle, -1.0f, res.data() );
+  if( rc ) { complain( "augment_models" ); return rc; }
+  struct Out { rsd_vec3_t *p, *q, *c; float *r, *ql; int32_t *cl, *in; int64_t n; };
+  std::vector<Out> outs( (size_t)P, Out{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0 } );
+  int failed = 0;
+  for( int p = 0; p < P; ++p )
+  {
+    const Shape M = model_from[p] < 0 ? model[(size_t)p] : shape[(size_t)model_from[p]];
+    if( !res[(size_t)p].cloud || failed ) { shape[(size_t)p] = M; continue; }       // no point carries uidx: the model stays (database_update.cpp:58)
+    const int64_t n_a = res[(size_t)p].n_extracted;
+    const size_t n = (size_t)n_a + (size_t)M.n;
+    Out& O = outs[(size_t)p];
+    O.p = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) ); O.q = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) ); O.c = (rsd_vec3_t*)malloc( n * sizeof(rsd_vec3_t) );
+    O.r = (float*)malloc( n * sizeof(float) ); O.ql = (float*)malloc( n * sizeof(float) );
+    O.cl = (int32_t*)malloc( n * sizeof(int32_t) ); O.in = (int32_t*)malloc( n * sizeof(int32_t) );
+    if( !( O.p && O.q && O.c && O.r && O.ql && O.cl && O.in ) || rs_hip_cloud_points( res[(size_t)p].cloud, (float*)O.p, (float*)O.q ) ) { failed = 1; continue; }
+    const std::vector<int32_t>& src = source[(size_t)p]; const std::vector<int32_t>& idx = scan_index[(size_t)p];
+    for( size_t i = 0; i < n; ++i )
+    {
+      const int32_t s = src[i];
+      if( s < n_a ) { const int32_t k = idx[(size_t)s]; O.c[i] = scan_col[k]; O.r[i] = scan_radii[k]; O.ql[i] = scan_qual[k]; O.cl[i] = scan_class[k]; }
+      else { const size_t k = (size_t)( s - n_a ); O.c[i] = M.col[k]; O.r[i] = M.radii[k]; O.ql[i] = M.qual[k]; O.cl[i] = M.cls[k]; }
+      O.in[i] = uidx[p];                                     // database_update.cpp:79-85
+    }
+    shape[(size_t)p] = Shape{ O.c, O.r, O.ql, O.cl, (int64_t)n }; O.n = (int64_t)n;
+  }
+  for( int p = 0; p < P; ++p ) if( res[(size_t)p].cloud ) rs_hip_cloud_destroy( res[(size_t)p].cloud );
+  if( failed )
+  {
+    for( Out& O : outs ) { free( O.p ); free( O.q ); free( O.c ); free( O.r ); free( O.ql ); free( O.cl ); free( O.in ); }
+    complain( "augment_models" );
+    return RS_HIP_E_RUNTIME;
+  }
+  for( int p = 0; p < P; ++p )
+  {
+    const Out& O = outs[(size_t)p];
+    out_pos[p] = O.p; out_nor[p] = O.q; out_col[p] = O.c; out_radii[p] = O.r; out_qual[p] = O.ql; out_class[p] = O.cl; out_instance[p] = O.in;
+    out_n[p] = O.n;
+    if( xforms ) std::memcpy( xforms[p].data, res[(size_t)p].xform, 64 );
+  }
+  return 0;
+}
+
 int32_t rsd_scan_to_objects( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const int32_t* class_ids, const int32_t* instance_ids, int64_t n,
                              const int32_t* static_classes, int32_t n_static, int32_t capacity,
                              int32_t* inst_ids, int32_t* class_of, int64_t* offsets, int32_t* order,

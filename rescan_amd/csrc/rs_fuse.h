@@ -19,6 +19,7 @@ namespace rs {
 namespace fuse {
 
 constexpr int64_t MAX_POINTS = 1ll << 24;
+constexpr int64_t MAX_TOTAL = 2147483646ll;   // all placements of one segmented call together: an int32 index names every element
 constexpr uint32_t SEED_MERGE = 12346u;       // rs_pointcloud.h:428
 constexpr int JUMP_BITS = 24;                 // step i uses draw n-1-i <= 2^24 - 2
 

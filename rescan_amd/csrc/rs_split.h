@@ -24,6 +24,8 @@
 #include <unordered_map>
 #include <vector>
 
+struct ihipStream_t;                             // (hipStream_t's target: this header needs no HIP)
+
 namespace rs {
 namespace split {
 
@@ -163,6 +165,12 @@ inline int plan( const float* pos, const float* nor, const int32_t* class_ids, c
   if( P.order && n > 0 ) std::memcpy( P.order, order.data(), (size_t)n * 4 );
   return RS_HIP_OK;
 }
+
+// The device route's table and stable partition for a caller in another unit (rs_fuse.hip: the arrangement call), defined in
+// rs_split.hip: the n >= 1 ids (host) are uploaded once; T is the table in order of first appearance, offsets its n_instances + 1
+// segment starts, and *order (device, n entries, the unit's workspace: valid until the thread's next split call) holds segment k at
+// [offsets[k], offsets[k + 1]) — by contract what rs_hip_select_by_ids returns for T.ids[k].  RS_HIP_E_CAPACITY above MAX_INSTANCES.
+int segments_device( const int32_t* instance_ids, int n, Table& T, std::vector<int64_t>& offsets, const int32_t** order, ihipStream_t* st );
 
 } // namespace split
 } // namespace rs

@@ -649,6 +649,21 @@ int split_check_out( const rs_hip_split_out_t* out, int64_t n )
 
 } // namespace
 
+// (rs_split.h) steps 1 and 2 alone, for rs_fuse.hip's arrangement call
+int rs::split::segments_device( const int32_t* instance_ids, int n, Table& T, std::vector<int64_t>& offsets, const int32_t** order, ihipStream_t* st )
+{
+  SplitWorkspace& W = g_split_ws;
+  RS_TRY( W.ids.ensure( (size_t)n * 4 ), "split: buffers" );
+  RS_TRY( hipMemcpyAsync( W.ids.p, instance_ids, (size_t)n * 4, hipMemcpyHostToDevice, st ), "split: upload" );
+  int rc = split_table_device( W.ids.as<int32_t>(), n, T, st ); if( rc ) { (void)hipStreamSynchronize( st ); return rc; }
+  const size_t I = T.ids.size();
+  rc = split_partition_device( W.ids.as<int32_t>(), n, (int)I, st ); if( rc ) { (void)hipStreamSynchronize( st ); return rc; }
+  offsets.assign( I + 1, 0 );
+  for( size_t k = 0; k < I; ++k ) offsets[k + 1] = offsets[k] + T.counts[k];
+  *order = W.order.as<int32_t>();
+  return RS_HIP_OK;
+}
+
 extern "C" {
 
 int rs_hip_split_plan( const float* pos, const float* nor, const int32_t* class_ids, const int32_t* instance_ids, int64_t n,

@@ -18,6 +18,12 @@ Fixtures (tests/test_fuse_cpu.py, tests/test_gpu_fuse.py compare every array bit
   fuse_hostile  rs_pointcloud_transform of the points of tests/hard_fuse.py (+-0, subnormal, Inf, NaN, FLT_MAX coordinates; and a
               finite set) under each of its transforms: identity, a translation of 1e4, a rotation, scales of 1e-20 and 1e20, a
               matrix of -0.0, a translation of Inf and NaN.
+  fuse_arrangement  the whole loop over an arrangement of five placements in a small room (floor, two walls, a chair, a table), in
+              loop order: the chair (dynamic, its pose perturbed), a wall (static), a uidx no scan point carries, the table (dynamic),
+              and a novel copy of the chair whose model is what the chair's placement left (model_from = 0: the reference's :51
+              after :89) — its model arrays are the first placement's merged arrays, fed back through the same functions.  Per
+              placement p: p<k>_model_* (where model_from is -1), p<k>_extracted_*, p<k>_merged_*, p<k>_xform, p<k>_icp_err; and
+              uidx, is_static, model_from, poses, n_extracted for all.
 
     python tools/fuse_fixture/gen.py --time
 
@@ -209,6 +215,63 @@ def write_hostile(L, out_dir):
     print(f"hostile: {len(out['a_pos'])} points x {len(out['names'])} transforms, twice, {size} bytes -> {path}")
 
 
+def write_arrangement(L, out_dir):
+    """fuse_arrangement: rsdu_augment_database's loop, placement by placement through fx_augment, a merged result chained in as a
+    later placement's model."""
+    rng = np.random.default_rng(406)
+    s = synth.make_scene(seed=23, width=2.0, depth=2.0, height=0.6, density=330.0, objects=("chair", "table"))
+    scan = attributes(rng, s["points"], s["normals"], s["class_idx"], s["instance_idx"])
+    chair, table = s["objects"]
+    assert chair["kind"] == "chair" and len(np.unique(scan["inst"])) == 5 and 2000 <= len(scan["pos"]) <= 9000, len(scan["pos"])
+
+    def model_of(o):
+        return attributes(rng, o["pos"], o["nor"], np.full(len(o["pos"]), o["class_idx"]), np.full(len(o["pos"]), o["uidx"]))
+    wall_pose = synth.pose_matrix(0.3, (0.5, 0.0, 0.2))
+    wall = synth.make_room_shell(np.random.default_rng(407), 2.0, 2.0, 0.6, 120.0)[1]
+    inv = np.linalg.inv(wall_pose.astype(np.float64).reshape(4, 4).T).T.ravel().astype(F)
+    wall_model = attributes(rng, synth.apply_pose(inv, wall[0]), synth.apply_pose(inv, wall[1], False), np.full(len(wall[0]), 1), np.full(len(wall[0]), 1))
+    # (uidx, is_static, model_from, model, pose)
+    plan = [(chair["uidx"], 0, -1, model_of(chair), synth.perturbed_pose(chair["pose"], rng)),
+            (1, 1, -1, wall_model, wall_pose),
+            (99, 0, -1, model_of(table), table["pose"]),
+            (table["uidx"], 0, -1, model_of(table), synth.perturbed_pose(table["pose"], rng)),
+            (chair["uidx"], 0, 0, None, synth.perturbed_pose(chair["pose"], rng))]
+    out = {"scan_" + k: scan[k] for k in KEYS}
+    shapes, n_ext_all = [], []
+    for p, (uidx, is_static, model_from, model, pose) in enumerate(plan):
+        if model_from >= 0:
+            model = shapes[model_from]                                                  # the shape that placement left
+            assert len(model["pos"]) == len(out[f"p{model_from}_merged_pos"]), "the dependent placement's model is not the merged cloud"
+        else:
+            out.update({f"p{p}_model_" + k: model[k] for k in KEYS})
+        r = augment(L, scan, model, pose, uidx, is_static)
+        n_ext = len(r["extracted"]["pos"])
+        assert n_ext == int((scan["inst"] == uidx).sum())
+        n_ext_all.append(n_ext)
+        out.update({f"p{p}_extracted_" + k: r["extracted"][k] for k in KEYS})
+        out[f"p{p}_xform"], out[f"p{p}_icp_err"] = r["xform"], r["err"]
+        if r["merged"] is None:
+            assert n_ext == 0
+            shapes.append(model)                                                        # database_update.cpp:58: the object stays
+            continue
+        assert len(r["merged"]["pos"]) == n_ext + len(model["pos"]) and (r["merged"]["inst"] == uidx).all()
+        if not is_static:
+            assert 0 < n_ext <= 16384, n_ext
+        out.update({f"p{p}_merged_" + k: r["merged"][k] for k in KEYS})
+        shapes.append(r["merged"])
+    assert n_ext_all[2] == 0 and "p2_merged_pos" not in out and n_ext_all[1] > 0 and float(out["p1_icp_err"]) == 0.0
+    start = np.linalg.inv(plan[0][4].astype(np.float64).reshape(4, 4).T).T.ravel()
+    moved = float(np.linalg.norm(out["p0_xform"].astype(np.float64) - start))
+    assert moved > 1e-3, moved
+    assert len(out["p4_merged_pos"]) == n_ext_all[4] + len(out["p0_merged_pos"])
+    out.update(uidx=np.array([q[0] for q in plan], np.int32), is_static=np.array([q[1] for q in plan], np.int32),
+               model_from=np.array([q[2] for q in plan], np.int32), poses=np.stack([q[4] for q in plan]).astype(F),
+               n_extracted=np.array(n_ext_all, np.int64), max_dist=F(0.05), max_angle=F(10.0 * 0.005555555556 * np.pi))
+    path, size = save(out_dir, "arrangement", out)
+    print(f"arrangement: {len(scan['pos'])} scan points, extracted {n_ext_all}, merged {[len(x['pos']) for x in shapes]}, the chair's pose moved by "
+          f"{moved:.4f} (Frobenius), {size} bytes -> {path}")
+
+
 def time_reference(L):
     import fuse_timing as T
     rng = np.random.default_rng(405)
@@ -227,7 +290,7 @@ def main():
     ap.add_argument("--time", action="store_true", help="only print the reference's CPU times for the placements of tools/fuse_timing.py")
     ap.add_argument("--ref", default=os.environ.get("REF", "/root/reference"))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
-    ap.add_argument("--only", default="", help="write this fixture alone (perm, chair, wall, hostile)")
+    ap.add_argument("--only", default="", help="write this fixture alone (perm, chair, wall, hostile, arrangement)")
     a = ap.parse_args()
     here = os.path.dirname(os.path.abspath(__file__))
     with tempfile.TemporaryDirectory() as tmp:
@@ -237,7 +300,8 @@ def main():
         L = load(lib)
         if a.time:
             return time_reference(L)
-        for name, write in (("perm", write_perm), ("chair", write_chair), ("wall", write_wall), ("hostile", write_hostile)):
+        for name, write in (("perm", write_perm), ("chair", write_chair), ("wall", write_wall), ("hostile", write_hostile),
+                            ("arrangement", write_arrangement)):
             if a.only in ("", name):
                 write(L, a.out)
 
