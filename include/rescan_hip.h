@@ -78,6 +78,19 @@ typedef struct rs_hip_cloud rs_hip_cloud_t;
 
 rs_hip_cloud_t* rs_hip_cloud_create( const float* pos, const float* nor /* may be NULL */,
                                      int32_t n, float cell_size );
+/* rs_hip_cloud_create for n_clouds clouds in one call. pos[k] / nor[k]: n[k] x 3 floats (nor == NULL: no cloud has normals;
+ * nor[k] == NULL: cloud k has none; n[k] == 0: an empty cloud, pos[k] may be NULL). cell_sizes[k] as rs_hip_cloud_create's
+ * cell_size (NULL: -1 for all). out[k]: a cloud whose layouts, host copies and reported sizes are those of
+ * rs_hip_cloud_create( pos[k], nor[k], n[k], cell_sizes[k] ), to the byte. All or nothing: RS_HIP_OK, or an error code with out
+ * untouched and nothing left allocated.  The stages of the build run once for the whole batch (the number of launches and
+ * synchronisations does not grow with n_clouds), and the clouds of a batch share one device allocation, which is freed when the
+ * last of them is destroyed; each is destroyed by rs_hip_cloud_destroy like any other. */
+int             rs_hip_cloud_create_many( const float* const* pos, const float* const* nor, const int32_t* n, const float* cell_sizes,
+                                          int32_t n_clouds, rs_hip_cloud_t** out );
+/* A cloud of more than n points inside a batch is built alone, by rs_hip_cloud_create's own path (the result is the same).  Process-wide;
+ * n < 0 only reads; returns the previous value.  Default: 499 999 — at 500 000 points the batch no longer beat the single builds
+ * (profiles/r25/build_many_timing.txt). */
+int32_t         rs_hip_cloud_many_single_above( int32_t n );
 void            rs_hip_cloud_destroy( rs_hip_cloud_t* c );
 int32_t         rs_hip_cloud_size( const rs_hip_cloud_t* c );
 /* query tiles of the cloud: runs of at most 64 points of its Hilbert order, what one wave of a search takes */
@@ -616,7 +629,7 @@ typedef struct rs_hip_fuse_result {
  * the device: the scan's instance ids are uploaded once and cut by the split's table and stable partition (segment k of its
  * order is what rs_hip_select_by_ids returns for that id); the placements run in rounds by the depth of their model_from
  * chains (an ordinary arrangement is one round); a round runs one rs_hip_icp_align per dynamic placement, then ONE
- * permutation pass and ONE merge launch for all its placements, then one index build per merged cloud.  Two placements with
+ * permutation pass and ONE merge launch for all its placements, then one batched index build for its merged clouds.  Two placements with
  * the same uidx extract the same points.  Every result is bit for bit rs_hip_cloud_create_fused's for that placement alone
  * wherever that call is bit for bit the reference; above 16 384 extracted points xform is within the ICP's 1e-4 bar and
  * the merged arrays are bit for bit the merge under the xform returned.

@@ -31,6 +31,8 @@ SIGNATURES = {
     "rs_hip_profile_reset": (C.c_int, []),
     "rs_hip_profile_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "rs_hip_cloud_create": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float]),
+    "rs_hip_cloud_create_many": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "rs_hip_cloud_many_single_above": (C.c_int32, [C.c_int32]),
     "rs_hip_cloud_destroy": (None, [C.c_void_p]),
     "rs_hip_profile_marker": (C.c_int, []),
     "rs_hip_cloud_size": (C.c_int32, [C.c_void_p]),
@@ -295,6 +297,31 @@ class Cloud:
             self.n, float(cell_size))
         if not self.handle:
             raise RescanHipError("rs_hip_cloud_create failed: " + lib.rs_hip_last_error().decode())
+
+    @classmethod
+    def many(cls, clouds, cell_size=-1.0):
+        """Cloud(pos, nor, cell_size) for every (pos, nor_or_None) pair of `clouds`, built together in one call
+        (rs_hip_cloud_create_many): each cloud is, to the byte, what Cloud(...) makes of its pair.  cell_size: one value for all, or
+        one per cloud.  Returns the list of clouds; all or nothing."""
+        lib = load()
+        pairs = [(_f32(p).reshape(-1, 3), None if n is None else _f32(n).reshape(-1, 3)) for p, n in clouds]
+        k = len(pairs)
+        cells = np.full(k, cell_size, np.float32) if np.ndim(cell_size) == 0 else np.ascontiguousarray(cell_size, np.float32).ravel()
+        if len(cells) != k:
+            raise ValueError("one cell size per cloud")
+        pos = (C.c_void_p * max(k, 1))(*[p.ctypes.data for p, _ in pairs])
+        nor = (C.c_void_p * max(k, 1))(*[None if n is None else n.ctypes.data for _, n in pairs])
+        counts = np.array([len(p) for p, _ in pairs], np.int32)
+        handles = (C.c_void_p * max(k, 1))()
+        any_nor = any(n is not None for _, n in pairs)
+        _check(lib.rs_hip_cloud_create_many(C.addressof(pos), C.addressof(nor) if any_nor else None, counts.ctypes.data, cells.ctypes.data,
+                                            k, C.addressof(handles)))
+        made = []
+        for j, (p, n) in enumerate(pairs):
+            self = cls.__new__(cls)
+            self.handle = handles[j]; self.n = len(p); self._pos = p; self._nor = n
+            made.append(self)
+        return made
 
     @classmethod
     def level_of(cls, base, radius, max_n_neigh, cell_size=-1.0):
@@ -916,6 +943,12 @@ def cloud_build_seconds(reset=False):
     out = (C.c_double * 4)()
     n = load().rs_hip_cloud_build_seconds(out, 1 if reset else 0)
     return [float(x) for x in out], int(n)
+
+
+def cloud_many_single_above(n=-1):
+    """Clouds of more than n points inside a Cloud.many batch are built alone (rs_hip_cloud_many_single_above; the result is the
+    same).  n < 0 only reads.  Returns the previous value."""
+    return int(load().rs_hip_cloud_many_single_above(int(n)))
 
 
 def switch_get(name):

@@ -75,6 +75,12 @@ struct ProfScope
 
 } // namespace rs
 
+namespace rs {
+// One device allocation that holds every array of the clouds a batched build made together (cloud_create_many_impl); the last of
+// them that is destroyed frees it.
+struct CloudBlock { void* p = nullptr; std::atomic<int> clouds{ 0 }; };
+} // namespace rs
+
 struct rs_hip_cloud
 {
   int32_t n = 0;
@@ -97,6 +103,7 @@ struct rs_hip_cloud
   int64_t occupied = 0;             // occupied cells as handed to query_extent_limit (brute layout: the estimate of a 0.1 m grid)
   float extent_limit = 0.0f;        // the tile extent limit the query layout was cut with
   int64_t bytes = 0;
+  rs::CloudBlock* block = nullptr;  // null: the d_* arrays are allocations of this cloud's own; else sub-ranges of the block
   // as an ICP source whose centroid chains gave a problem up (sums that hover around zero: rs_hip_icp_align_batch): the next calls
   // this many go straight to pass 2 of the replay instead of paying for the attempt first
   mutable std::atomic<int> chains_wander{ 0 };
@@ -106,6 +113,11 @@ namespace rs {
 
 // rs_hip_cloud_create (from_device: pos / nor are device pointers — a level gathered on the device); null on failure
 rs_hip_cloud_t* cloud_create_impl( const float* pos, const float* nor, int32_t n, float cell_size, bool from_device );
+
+// rs_hip_cloud_create_many: the clouds of K segments built together, each to the byte what cloud_create_impl makes of its segment.
+// All or nothing: RS_HIP_OK and out[0 .. K) set, or an error code, rs_hip_last_error()'s text and out untouched.
+struct ManyInput { const float* pos; const float* nor; int32_t n; float cell_size; };
+int cloud_create_many_impl( const ManyInput* segments, int32_t n_segments, bool from_device, rs_hip_cloud_t** out );
 
 inline float radius_sq_of( float r ) { return (float)( (double)r * (double)r ); }   // msh_hash_grid.h:1104,1111 + :828
 

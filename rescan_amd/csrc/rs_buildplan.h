@@ -209,4 +209,27 @@ inline float query_extent_limit( int32_t n, size_t occupied_cells, float cell, f
   return extent_max < lo ? extent_max : lo;
 }
 
+// ---- the batched build (cloud_create_many_impl) ----
+// A batch is cut into groups of consecutive clouds that are built together.  The budgets of a group:
+#define RS_BP_MANY_POINTS_MAX 67108864.0        // 2^26 points: every index of a group's concatenated arrays fits an int32 with room to spare
+#define RS_BP_MANY_TRIAL_WORDS_MAX 67108864.0   // 2^26 words (256 MiB) of trial bit tables side by side; one table is at most 2^25 + 2
+#define RS_BP_MANY_CELL_WORDS_MAX 268435456.0   // 2^28 words (1 GiB) of offset tables: one scan (an int count) runs over all of them
+// The grouping rule, greedy and in order: cloud k joins the open group unless one of the two totals would then pass its budget; then
+// it opens the next.  cost_a / cost_b: what each cloud adds (points and words; either may be null: nothing).  group_end[g] = one
+// past the last cloud of group g; returns the number of groups.  Every cloud is in exactly one group, the groups are in order, and a
+// group is within both budgets unless it is ONE cloud that passes a budget alone (it is then built by itself).
+inline int bp_many_groups( const double* cost_a, const double* cost_b, int n_clouds, double budget_a, double budget_b, int* group_end )
+{
+  int groups = 0, open = 0;           // open: clouds in the open group
+  double a = 0.0, b = 0.0;
+  for( int k = 0; k < n_clouds; ++k )
+  {
+    const double ca = cost_a ? cost_a[k] : 0.0, cb = cost_b ? cost_b[k] : 0.0;
+    if( open && ( a + ca > budget_a || b + cb > budget_b ) ) { group_end[groups++] = k; open = 0; a = b = 0.0; }
+    a += ca; b += cb; ++open;
+  }
+  if( open ) group_end[groups++] = n_clouds;
+  return groups;
+}
+
 } // namespace rs

@@ -317,6 +317,45 @@ int    build_sort_pairs( void* tmp, size_t bytes, const uint32_t* kin, uint32_t*
 size_t build_scan_temp_bytes( size_t n );
 int    build_exclusive_scan( void* tmp, size_t bytes, const uint32_t* in, uint32_t* out, size_t n, hipStream_t st );
 
+// The same build for many clouds at once (rs_build.hip, cloud_create_many_impl): their points lie concatenated, a lane finds its
+// cloud in segid[], and a cloud's row of the segment table says where its points start and where its arrays go.
+struct ManySeg
+{
+  int      base, n;                 // its points in the concatenated arrays
+  int      has_nor, pad_;
+  float    mn[3], inv_cell;         // the offset table's cells (inv_cell 0: one cell)
+  int      dims[3];
+  float    hscale, extent_limit;    // Hilbert scale; the tile extent limit
+  float    pad2_;
+  unsigned long long cell_word;     // where its offset table starts in the group's table region, in words
+  float4   *pos, *nor, *qpos, *qnor;
+  uint32_t *tiles;
+  int      *by_orig;
+};
+struct ManyTrial                    // a cloud's trial grid of the current attempt (active 0: none)
+{
+  float    mn[3], inv, top[3];
+  int      active;
+  unsigned long long db, dc, word;  // word: where its bit table starts
+};
+void   launch_many_segids( const int* offsets, int n_clouds, int n, int* segid, hipStream_t st );
+void   launch_many_bounds( const float* pos3, const float* nor3, const int* segid, const ManySeg* segs, int n, unsigned* out8, hipStream_t st );
+void   launch_many_mark( const float* pos3, const int* segid, const ManyTrial* trial, int first, int count, uint32_t* bits, hipStream_t st );
+void   launch_many_popcount( const uint32_t* bits, unsigned long long n_words, const unsigned long long* table_start, const int* table_seg, int n_tables,
+                             int* occupied /* per cloud, zero on entry */, hipStream_t st );
+void   launch_many_cellids( const float* pos3, const int* segid, const ManySeg* segs, int first, int count, unsigned long long* key, uint32_t* local,
+                            uint32_t* tables, hipStream_t st );
+void   launch_many_gather( const float* pos3, const float* nor3, const int* segid, const ManySeg* segs, const uint32_t* order, int first, int count,
+                           bool query_layout, hipStream_t st );
+void   launch_many_count_runs( const unsigned long long* sorted, const int* segid, int first, int count, int* occupied, hipStream_t st );
+void   launch_many_hilbert( const float* pos3, const int* segid, const ManySeg* segs, int first, int count, unsigned long long* key, uint32_t* local, hipStream_t st );
+void   launch_many_tile_flags( const int* segid, const ManySeg* segs, int first, int count, uint32_t* flags, uint32_t* jump_a, uint32_t* jump_b, hipStream_t st );
+void   launch_many_tile_scatter( const uint32_t* flags, const uint32_t* scanned, const int* segid, const ManySeg* segs, int first, int count,
+                                 int seg_first, int seg_count, int* n_tiles, hipStream_t st );
+size_t build_sort64_temp_bytes( int n, int bits );
+int    build_sort64_pairs( void* tmp, size_t bytes, const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout, int n,
+                           int bits, hipStream_t st );
+
 // Neighbourhood graph (rspf_compute_neighborhood): from self-search rows to unique weighted edges.
 // Level builder (lib/rs/rs_pointcloud.h:984-1106): a self-search of one cloud listing, per point, the LATER points
 // (larger original index) within the radius, then a propagation of decisions along those rows (rs_rows.hip).

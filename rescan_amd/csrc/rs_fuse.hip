@@ -774,6 +774,9 @@ int rs_hip_cloud_fuse_arrangement( const rs_hip_cloud_t* scan, const int32_t* sc
     std::vector<int64_t> sizes( Q );
     std::vector<const rs_hip_cloud_t*> model( Q );
     // 2. xform = inverse( pose ), refined by ICP against the model unless the object is static (database_update.cpp:62-68)
+    std::vector<int64_t> src_first, src_count;        // the refined placements' extracted points, side by side in the level workspace
+    std::vector<size_t> refined;
+    int64_t src_total = 0;
     for( size_t k = 0; k < Q; ++k )
     {
       const int p = list[k];
@@ -787,24 +790,35 @@ int rs_hip_cloud_fuse_arrangement( const rs_hip_cloud_t* scan, const int32_t* sc
       G.b.qpos = M.qpos; G.b.qnor = M.qnor; G.b.by_orig = M.by_orig;
       G.n_a = (int)na;
       sizes[k] = na + (int64_t)M.n;
-      float* xform = &xforms[16 * (size_t)p];
-      rs_hip_mat4_inverse( pl.pose, xform );
-      if( pl.refine )
+      rs_hip_mat4_inverse( pl.pose, &xforms[16 * (size_t)p] );
+      if( pl.refine ) { refined.push_back( k ); src_first.push_back( src_total ); src_count.push_back( na ); src_total += na; }
+    }
+    if( !refined.empty() )        // (src_total is below the round's merged total, which an int32 index names)
+    {
+      // the ICP sources of the round: one gather per placement into its segment, one batched index build, one ICP per placement
+      float *d_pos = nullptr, *d_nor = nullptr;
+      if( api_level_workspace( (size_t)src_total, true, &d_pos, &d_nor ) ) return undo( RS_HIP_E_RUNTIME );
+      for( size_t j = 0; j < refined.size(); ++j )
       {
-        float *d_pos = nullptr, *d_nor = nullptr;
-        if( api_level_workspace( (size_t)na, true, &d_pos, &d_nor ) ) return undo( RS_HIP_E_RUNTIME );
-        hipLaunchKernelGGL( k_fuse_gather, dim3( blocks_for( na, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, G.a, (int)na, d_pos, d_nor );
-        ARR_TRY( hipGetLastError(), "cloud_fuse_arrangement: gather launch" );
-        rs_hip_cloud_t* src = api_cloud_from_level_workspace( true, (int32_t)na, -1.0f );
-        if( !src ) return undo( RS_HIP_E_RUNTIME );
+        const int64_t na = src_count[j];
+        hipLaunchKernelGGL( k_fuse_gather, dim3( blocks_for( na, FUSE_BLOCK ) ), dim3( FUSE_BLOCK ), 0, st, seg[refined[j]].a, (int)na,
+                            d_pos + 3 * (size_t)src_first[j], d_nor + 3 * (size_t)src_first[j] );
+      }
+      ARR_TRY( hipGetLastError(), "cloud_fuse_arrangement: gather launch" );
+      std::vector<rs_hip_cloud_t*> src( refined.size(), nullptr );
+      if( int brc = api_clouds_from_device( d_pos, d_nor, src_first.data(), src_count.data(), (int32_t)refined.size(), -1.0f, src.data() ) ) return undo( brc );
+      int irc = RS_HIP_OK;
+      for( size_t j = 0; j < refined.size() && !irc; ++j )
+      {
+        const int p = list[refined[j]];
         const float identity[16] = { 1, 0, 0, 0,  0, 1, 0, 0,  0, 0, 1, 0,  0, 0, 0, 1 };
         int32_t iters = 0;
-        const int irc = rs_hip_icp_align( src, model[k], xform, identity, max_dist, max_angle, 100, 0, &errs[(size_t)p], &iters );
-        rs_hip_cloud_destroy( src );
-        if( irc ) return undo( irc );
+        irc = rs_hip_icp_align( src[j], model[refined[j]], &xforms[16 * (size_t)p], identity, max_dist, max_angle, 100, 0, &errs[(size_t)p], &iters );
       }
-      std::memcpy( G.x.m, xform, 64 );
+      for( rs_hip_cloud_t* c : src ) rs_hip_cloud_destroy( c );
+      if( irc ) return undo( irc );
     }
+    for( size_t k = 0; k < Q; ++k ) std::memcpy( seg[k].x.m, &xforms[16 * (size_t)list[k]], 64 );
     lap( 1 );
     // 3. all permutations of the round, 4. one merge launch into the concatenation
     FuseSegPlan L;
@@ -817,16 +831,13 @@ int rs_hip_cloud_fuse_arrangement( const rs_hip_cloud_t* scan, const int32_t* sc
       if( results[list[k]].source )
         ARR_TRY( hipMemcpyAsync( results[list[k]].source, W.perm.as<int32_t>() + L.off[k], (size_t)sizes[k] * 4, hipMemcpyDeviceToHost, st ), "cloud_fuse_arrangement: download" );
     lap( 3 );
-    // 5. one index build per merged cloud, its slice copied to where the build reads (each build synchronises the stream)
-    for( size_t k = 0; k < Q; ++k )
+    // 5. one batched index build for the round's merged clouds, read from the concatenation where the merge left them
     {
-      float *d_pos = nullptr, *d_nor = nullptr;
-      if( api_level_workspace( (size_t)sizes[k], true, &d_pos, &d_nor ) ) return undo( RS_HIP_E_RUNTIME );
-      ARR_TRY( hipMemcpyAsync( d_pos, W.out_pos.as<float>() + 3 * (size_t)L.off[k], (size_t)sizes[k] * 12, hipMemcpyDeviceToDevice, st ), "cloud_fuse_arrangement: slice" );
-      ARR_TRY( hipMemcpyAsync( d_nor, W.out_nor.as<float>() + 3 * (size_t)L.off[k], (size_t)sizes[k] * 12, hipMemcpyDeviceToDevice, st ), "cloud_fuse_arrangement: slice" );
-      rs_hip_cloud_t* c = api_cloud_from_level_workspace( true, (int32_t)sizes[k], cell_size );
-      if( !c ) return undo( RS_HIP_E_RUNTIME );
-      made[(size_t)list[k]] = c; shape[(size_t)list[k]] = c;
+      std::vector<int64_t> at( Q );
+      std::vector<rs_hip_cloud_t*> merged( Q, nullptr );
+      for( size_t k = 0; k < Q; ++k ) at[k] = L.off[k];
+      if( int brc = api_clouds_from_device( W.out_pos.as<float>(), W.out_nor.as<float>(), at.data(), sizes.data(), (int32_t)Q, cell_size, merged.data() ) ) return undo( brc );
+      for( size_t k = 0; k < Q; ++k ) { made[(size_t)list[k]] = merged[k]; shape[(size_t)list[k]] = merged[k]; }
     }
     lap( 4 );
   }

@@ -22,6 +22,11 @@ void            api_prof_end( const char* name, void* begin );   // ... and the 
 int             api_level_workspace( size_t n, bool with_nor, float** pos, float** nor );
 // ... and the cloud over the n points written there (the index build of rs_hip_cloud_create_level); null on failure
 struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n, float cell_size );
+// one cloud per segment of device arrays (packed xyz; nor may be null), segment k being the points [first[k], first[k] + count[k]): the
+// batched index build of rs_hip_cloud_create_many; all or nothing: RS_HIP_OK and out[0 .. n_segments) set, or an error code and out
+// untouched.  Synchronises the stream.
+int             api_clouds_from_device( const float* pos, const float* nor, const int64_t* first, const int64_t* count, int32_t n_segments, float cell_size,
+                                        struct ::rs_hip_cloud** out );
 // a cloud's points for a reader in another unit (rs_fuse.hip): the query layout (Hilbert order, 16-byte records) and the map from an
 // original index to its slot there; nor is null for a cloud without normals
 struct CloudPoints { const float4* qpos; const float4* qnor; const int* by_orig; int n; };

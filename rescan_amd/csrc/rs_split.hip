@@ -356,12 +356,12 @@ __global__ __launch_bounds__( 64 ) void k_split_chains_lone( SplitSrc S, const i
   sums[c] = sum;
 }
 
-// One lane per output point: point first + t of the instance-major order, written at t.  fixed_k >= 0: all of them belong to that
-// instance; otherwise the instance is found in offsets (n_instances + 1 entries).
+// One lane per output point: point first + t of the instance-major order, written at t; its instance is found in offsets
+// (n_instances + 1 entries).
 struct SplitApplyArgs
 {
   SplitSrc S; const int32_t* order; const long long* offsets; const float* xforms; const int32_t* is_static;
-  int n_instances, fixed_k; long long first, count; float* out_pos; float* out_nor;
+  int n_instances; long long first, count; float* out_pos; float* out_nor;
 };
 
 __global__ __launch_bounds__( SPLIT_BLOCK ) void k_split_apply( SplitApplyArgs A )
@@ -369,13 +369,9 @@ __global__ __launch_bounds__( SPLIT_BLOCK ) void k_split_apply( SplitApplyArgs A
   const long long t = (long long)blockIdx.x * SPLIT_BLOCK + threadIdx.x;
   if( t >= A.count ) return;
   const long long i = A.first + t;
-  int k = A.fixed_k;
-  if( k < 0 )
-  {
-    int lo = 0, hi = A.n_instances;                                        // the last k with offsets[k] <= i
-    while( hi - lo > 1 ) { const int mid = ( lo + hi ) >> 1; if( A.offsets[mid] <= i ) lo = mid; else hi = mid; }
-    k = lo;
-  }
+  int lo = 0, hi = A.n_instances;                                          // the last k with offsets[k] <= i
+  while( hi - lo > 1 ) { const int mid = ( lo + hi ) >> 1; if( A.offsets[mid] <= i ) lo = mid; else hi = mid; }
+  const int k = lo;
   int o = A.order[i];
   if( (unsigned)o >= (unsigned)A.S.n ) o = 0;
   float p[3], q[3] = { 0.0f, 0.0f, 0.0f };
@@ -636,7 +632,7 @@ SplitApplyArgs split_apply_args( const SplitSrc& S, int n_instances )
   SplitWorkspace& W = g_split_ws;
   SplitApplyArgs A{};
   A.S = S; A.order = W.order.as<int32_t>(); A.offsets = W.offsets.as<long long>(); A.xforms = W.xforms.as<float>(); A.is_static = W.is_static.as<int32_t>();
-  A.n_instances = n_instances; A.fixed_k = -1;
+  A.n_instances = n_instances;
   return A;
 }
 
@@ -864,27 +860,21 @@ int rs_hip_cloud_split_objects( const rs_hip_cloud_t* scan, const int32_t* class
     RS_TRY_DRAIN( st, hipMemcpyAsync( order.data(), W.order.p, (size_t)n * 4, hipMemcpyDeviceToHost, st ), "cloud_split_objects: download" );
     RS_TRY( hipStreamSynchronize( st ), "cloud_split_objects: download" );
   }
+  // every instance into one workspace, instance after instance, in one launch; then one batched index build over its segments
   const int I = (int)T.ids.size();
-  std::vector<rs_hip_cloud_t*> made;
-  auto undo = [&]() { for( rs_hip_cloud_t* c : made ) rs_hip_cloud_destroy( c ); (void)hipStreamSynchronize( st ); };
-  for( int k = 0; k < I; ++k )
+  std::vector<rs_hip_cloud_t*> made( (size_t)I, nullptr );
+  SplitApplyArgs A = split_apply_args( S, I );
+  A.first = 0; A.count = n;
+  if( api_level_workspace( (size_t)n, true, &A.out_pos, &A.out_nor ) ) { (void)hipStreamSynchronize( st ); return RS_HIP_E_RUNTIME; }
   {
-    const int64_t count = T.counts[(size_t)k];
-    SplitApplyArgs A = split_apply_args( S, I );
-    A.fixed_k = k; A.first = O.offsets[(size_t)k]; A.count = count;
-    if( api_level_workspace( (size_t)count, true, &A.out_pos, &A.out_nor ) ) { undo(); return RS_HIP_E_RUNTIME; }
-    {
-      ProfSpan span( "split_apply" );
-      hipLaunchKernelGGL( k_split_apply, dim3( blocks_for( count, SPLIT_BLOCK ) ), dim3( SPLIT_BLOCK ), 0, st, A );
-    }
-    if( hipGetLastError() != hipSuccess ) { undo(); return fail( RS_HIP_E_RUNTIME, "cloud_split_objects: apply launch" ); }
-    clk.lap( 3 );
-    // (synchronises the stream)
-    rs_hip_cloud_t* c = api_cloud_from_level_workspace( true, (int32_t)count, cell_size );
-    clk.lap( 4 );
-    if( !c ) { undo(); return RS_HIP_E_RUNTIME; }
-    made.push_back( c );
+    ProfSpan span( "split_apply" );
+    hipLaunchKernelGGL( k_split_apply, dim3( blocks_for( n, SPLIT_BLOCK ) ), dim3( SPLIT_BLOCK ), 0, st, A );
   }
+  RS_TRY_DRAIN( st, hipGetLastError(), "cloud_split_objects: apply launch" );
+  clk.lap( 3 );
+  rc = api_clouds_from_device( A.out_pos, A.out_nor, O.offsets.data(), T.counts.data(), I, cell_size, made.data() );      // (all or nothing)
+  clk.lap( 4 );
+  if( rc ) { (void)hipStreamSynchronize( st ); return rc; }
   for( int k = 0; k < I; ++k ) objects[k] = made[(size_t)k];
   if( out->order ) std::memcpy( out->order, order.data(), (size_t)n * 4 );
   split_write_outputs( T, O, out );
