@@ -1,8 +1,9 @@
-// What the four host units of the C ABI share — rs_api.hip, rs_icp_api.hip, rs_rows_api.hip and the host part of rs_score.hip — and
-// nobody else: the error text, the calling thread's stream, the growable buffers their workspaces are made of, profiling spans,
-// the cloud object, its construction, and the two rules every search launch takes its radius and its hand-off from.  Definitions:
-// rs_api.hip, except the trivial inlines.  Host only.  (The units with kernels AND entry points of their own include rs_host.h
-// instead, whose buffer and failure path have another return contract and message format: DESIGN.md §3.h.)
+// What the five host units of the C ABI share — rs_api.hip, rs_cloud_api.hip, rs_icp_api.hip, rs_rows_api.hip and the host part of
+// rs_score.hip — and nobody else: the error text, the calling thread's stream, the growable buffers their workspaces are made of,
+// profiling spans, the cloud object, its construction, and the two rules every search launch takes its radius and its hand-off from.
+// Definitions: a cloud's construction in rs_cloud_api.hip, the rest in rs_api.hip, except the trivial inlines.  Host only.  (The
+// units with kernels AND entry points of their own include rs_host.h instead, whose buffer and failure path have another return
+// contract and message format: DESIGN.md §3.h.)
 #pragma once
 #include "../../include/rescan_hip.h"
 #include "rs_device.h"

@@ -2,7 +2,8 @@
 // lib/msh/msh_hash_grid.h:388-541): bounds, the density-derived cell size, the cell-sorted target
 // layout with its dense offset table, and the Hilbert-ordered, tiled query layout — from the caller's
 // raw AoS arrays, uploaded once.  Sorting and scanning use hipCUB (rocPRIM) device primitives; the
-// kernels around them are below.  Orchestration (buffers, the few host decisions) is in rs_api.hip.
+// kernels around them are below.  Orchestration (buffers, launches) is in rs_cloud_api.hip, the few
+// host decisions between the kernels in rs_buildplan.h (CloudPlan).
 //
 // Nothing here decides a search result: results depend on neither the cell size, nor the order of
 // points inside a cell, nor the tiling.  The one expression that must agree with the search kernels is

@@ -1,6 +1,7 @@
-// The arithmetic of a cloud's index build: every expression of rs_api.hip (cloud_create_impl) and rs_build.hip that produces an
-// index or a size — the sanitised bounds, the trial grids of the density-derived cell and a point's cell in them, the cell size,
-// the offset table's dimensions, a stored point's cell, its Hilbert cell and key, the tile extent limit.  For the host and, under
+// The arithmetic of a cloud's index build: every expression of rs_cloud_api.hip (cloud_create_impl, many_build_group) and
+// rs_build.hip that produces an index or a size — the sanitised bounds, the trial grids of the density-derived cell and a point's
+// cell in them, the cell size, the offset table's dimensions, a stored point's cell, its Hilbert cell and key, the tile extent
+// limit — and the one statement of the host's decisions between the kernels (CloudPlan).  For the host and, under
 // hipcc, for the device (RS_HD, like rs_math.h); nothing of HIP is needed when a host compiler reads it, so that
 // tests/host/buildplan_check.cpp runs these very expressions under the sanitizers and tests/build_restate.py is held to them.
 //
@@ -12,6 +13,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 
 #ifndef RS_HD
 #if defined( __HIPCC__ )
@@ -37,6 +39,9 @@ RS_HD inline void bp_bounds_take( float v, float& lo, float& hi )
   if( v < lo ) lo = v;
   if( v > hi ) hi = v;
 }
+// the float of a word of the bounds kernels, which take minima and maxima of floats as unsigned atomics on an order-preserving
+// encoding (negative: every bit flipped, else the sign bit set)
+inline float bp_bounds_decode( unsigned u ) { const unsigned b = ( u & 0x80000000u ) ? ( u ^ 0x80000000u ) : ~u; float f; std::memcpy( &f, &b, 4 ); return f; }
 // an axis without a finite coordinate (lo > hi) gets [0, 0]
 inline void bp_sanitise_bounds( float mn[3], float mx[3] )
 {
@@ -207,6 +212,92 @@ inline float query_extent_limit( int32_t n, size_t occupied_cells, float cell, f
   const float spacing = cell / sqrtf( per_cell > 1.0f ? per_cell : 1.0f );
   const float want = 12.0f * spacing, lo = want > 0.25f ? want : 0.25f;
   return extent_max < lo ? extent_max : lo;
+}
+
+// ---- the plan of one cloud ----
+// What the host decides for one cloud, and the one statement of how: each function below covers what lies between two of a build's
+// device synchronisations.  The single build (cloud_create_impl) and the batched one (many_build_group) of rs_cloud_api.hip drive them
+// with their own launches around them, and tests/host/buildplan_check.cpp with loops over the points in the launches' place.
+struct CloudPlan
+{
+  float mn[3] = { 0, 0, 0 }, mx[3] = { 0, 0, 0 };       // sanitised bounds
+  float nor_max = 1.0f;                                 // max |normal|
+  float cell_size = 0.0f;                               // as asked, then as chosen; 0: the brute layout
+  float chosen = 0.0f;                                  // cell_size as it went into the table (given, or derived and scaled): the check's report
+  float c0 = 0.0f; bool undecided = false;              // the trial grid's cell while the density-derived cell is being looked for
+  float cell = 0.0f, inv_cell = 0.0f;                   // of the offset table (coarsened into its budget)
+  int dims[3] = { 1, 1, 1 };
+  size_t n_cells = 1, occupied = 0;
+  float extent_limit = 0.0f, hscale = 0.0f;             // of the query layout: the tile extent limit, the Hilbert scale
+};
+// after the bounds kernel: its eight words (min and max per axis in the order-preserving encoding, the largest |normal|^2 as a
+// float's bits, a flag for a normal that is not finite).  The kernel took the finite coordinates only; an axis without one: [0, 0].
+inline void bp_plan_bounds( CloudPlan& p, const unsigned got[8], int32_t n, bool has_nor )
+{
+  if( n <= 0 ) return;
+  for( int a = 0; a < 3; ++a ) { p.mn[a] = bp_bounds_decode( got[a] ); p.mx[a] = bp_bounds_decode( got[3 + a] ); }
+  bp_sanitise_bounds( p.mn, p.mx );
+  if( has_nor )
+  {
+    float n2; std::memcpy( &n2, &got[6], 4 );
+    p.nor_max = ( got[7] || !std::isfinite( n2 ) ) ? INFINITY : std::sqrt( n2 ) * 1.00001f;
+  }
+}
+// cell_size < 0: pick the cell from the cloud's own sampling density (about two sample spacings: a surface patch then holds ~4
+// points per cell, the first search shell ~100-300), over at most RS_BP_TRIAL_ATTEMPTS trial grids
+inline void bp_plan_cell_begin( CloudPlan& p, float cell_size, int32_t n )
+{
+  p.cell_size = cell_size;
+  if( !( cell_size < 0.0f ) ) return;
+  p.cell_size = 0.1f;
+  if( n > 0 ) { p.undecided = true; p.c0 = bp_trial_first_cell( p.mn, p.mx ); }
+}
+// one attempt of an undecided cloud, before the device: true, tg: count the occupied cells of this grid and call bp_plan_trial_counted.
+// false: the grid is too fine to count (huge, sparse extent): coarsened, or, at the last attempt, standing for the wanted density.
+inline bool bp_plan_trial( CloudPlan& p, bool last, TrialGrid& tg )
+{
+  tg = bp_trial_grid( p.mn, p.mx, p.c0 );
+  if( tg.countable() ) return true;
+  if( !last ) p.c0 *= 2.0f;
+  else { p.cell_size = bp_auto_cell_of( RS_BP_PER_CELL_WANTED, p.c0 ); p.undecided = false; }
+  return false;
+}
+// ... and after the count
+inline void bp_plan_trial_counted( CloudPlan& p, int32_t n, int occ, bool last )
+{
+  const float per_cell = bp_per_cell( n, occ );
+  if( per_cell >= RS_BP_PER_CELL_WANTED || last ) { p.cell_size = bp_auto_cell_of( per_cell, p.c0 ); p.undecided = false; }
+  else p.c0 *= 2.0f;
+}
+// the offset table (asked_auto: the caller's cell_size was < 0; auto_scale: RS_HIP_AUTO_CELL_SCALE)
+inline void bp_plan_table( CloudPlan& p, int32_t n, bool asked_auto, float auto_scale )
+{
+  if( asked_auto && n > 0 ) p.cell_size = bp_auto_cell_scaled( p.cell_size, auto_scale );
+  p.chosen = p.cell = p.cell_size;
+  if( p.cell_size > 0.0f && n > 0 )
+  {
+    // (in double before any cast: an extent of any size is coarsened into the table; one that overflows a float gets the brute layout)
+    if( bp_table_dims( p.mn, p.mx, p.cell, p.dims ) ) p.inv_cell = 1.0f / p.cell;
+    else p.cell_size = p.cell = 0.0f;
+  }
+  p.n_cells = (size_t)p.dims[0] * p.dims[1] * p.dims[2];
+}
+// the query layout, after the cell index (counted: its occupied cells; extent_max: RS_HIP_TILE_EXTENT_MAX): Hilbert order, tiles of
+// <= 64 points within the extent limit
+inline void bp_plan_query_layout( CloudPlan& p, int32_t n, size_t counted, float extent_max )
+{
+  p.occupied = counted;
+  const float lim_cell = p.cell_size > 0.0f ? p.cell : 0.1f;
+  if( !( p.cell_size > 0.0f ) ) p.occupied = bp_brute_occupied( n, p.mn, p.mx );
+  p.extent_limit = query_extent_limit( n, p.occupied, lim_cell, extent_max );
+  p.hscale = n > 0 ? bp_hilbert_scale( p.mn, p.mx ) : 0.0f;
+}
+// rs_hip_cloud_bytes: the cell-sorted records (16 bytes each, at least one) and the offset table | the same records in Hilbert
+// order, the tile list and the inverse of the order
+inline int64_t bp_plan_bytes( int32_t n, bool has_nor, size_t n_cells, int n_tiles )
+{
+  const size_t pb = (size_t)( n > 1 ? n : 1 ) * 16;
+  return (int64_t)( pb * ( has_nor ? 2 : 1 ) + ( n_cells + 1 ) * 4 ) + (int64_t)( pb * ( has_nor ? 2 : 1 ) + ( (size_t)n_tiles + 1 ) * 4 + (size_t)n * 4 );
 }
 
 // ---- the batched build (cloud_create_many_impl) ----

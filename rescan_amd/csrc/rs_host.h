@@ -2,7 +2,7 @@
 // rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip): what they need from the host side of the C ABI, a growable buffer, the failure
 // path, a profiling span and the grid size of a launch.  Host only: no kernel file needs it.  The api_* functions are defined by the unit
 // that owns what they reach: api_level_workspace / api_cloud_from_level_workspace in rs_rows_api.hip, api_score_poses_device in
-// rs_score.hip, the others in rs_api.hip.
+// rs_score.hip, api_cloud_* / api_clouds_from_device in rs_cloud_api.hip, the others in rs_api.hip.
 #pragma once
 #include "../../include/rescan_hip.h"
 #include "rs_device.h"

@@ -2,8 +2,8 @@
 //
 // Owns the ICP outer loop (searches and reductions on the GPU; the 6x6 LDLᵀ solve and the pose composition on the host in the
 // reference's own arithmetic, lib/rs/icp.h:267-295), the estimator policy that loop applies (icp_choose, icp_plain_iterations),
-// the call's one fill launch, the per-iteration traces and the diagnostics.  Runtime state, clouds and profiling: rs_api.hip,
-// through rs_api.h.
+// the call's one fill launch, the per-iteration traces and the diagnostics.  Runtime state and profiling: rs_api.hip, clouds:
+// rs_cloud_api.hip, both through rs_api.h.
 
 #include "../../include/rescan_hip.h"
 #include "rs_api.h"

@@ -18,6 +18,7 @@
 //   more than 128 bins, fewer than k points, a query outside the box) the answer is KnnGrid's: no bin cap, and the walk ends once
 //   every bin has been visited.
 
+#include "rs_buildplan.h"
 #include "rs_host.h"
 #include "rs_search.h"
 
@@ -334,11 +335,10 @@ int build_grid( rs_hip_knn_grid* G, const GridView& c, float radius, int32_t dim
     if( e == hipSuccess ) e = hipStreamSynchronize( st );
     (void)hipFree( d_box );
     if( e != hipSuccess ) return fail( RS_HIP_E_RUNTIME, "knn grid: bounds", e );
-    auto dec = []( unsigned u ) { const unsigned b = ( u & 0x80000000u ) ? ( u ^ 0x80000000u ) : ~u; float f; std::memcpy( &f, &b, 4 ); return f; };
     for( int a = 0; a < 3; ++a )
     {
       if( box[a] == ~0u ) continue;                                    // (every coordinate NaN)
-      const float lo = dec( box[a] ), hi = dec( box[3 + a] );
+      const float lo = bp_bounds_decode( box[a] ), hi = bp_bounds_decode( box[3 + a] );
       mn[a] = ( mn[a] > lo ) ? lo : mn[a]; mx[a] = ( mx[a] < hi ) ? hi : mx[a];      // against the reference's starting values
     }
     if( dim == 2 ) { mn[2] = 0.0f; mx[2] = 0.0f; }

@@ -1,9 +1,11 @@
 // librescan_hip host side: the entry points of include/rescan_hip.h over the kernels of rs_rows.hip — label transfer (with its
 // folds, ids and attribute gathers), generic radius-search rows, the neighbourhood graph, the level builder and the
-// scene-coverage term.  Host only: no kernel is defined here.  Runtime state, clouds and profiling: rs_api.hip, through rs_api.h.
+// scene-coverage term.  Host only: no kernel is defined here.  Runtime state and profiling: rs_api.hip, clouds:
+// rs_cloud_api.hip, both through rs_api.h.
 
 #include "../../include/rescan_hip.h"
 #include "rs_api.h"
+#include "rs_buildplan.h"
 #include "rs_device.h"
 #include "rs_host.h"
 #include "rs_math.h"
@@ -448,11 +450,10 @@ int rs_hip_radius_search( const rs_hip_cloud_t* target, const float* query, int6
   launch_build_bounds( d_raw, nullptr, nq, d_small, g_stream );
   HIP_TRY( hipMemcpyAsync( got, d_small, 32, hipMemcpyDeviceToHost, g_stream ), RS_HIP_E_RUNTIME );
   HIP_TRY( hipStreamSynchronize( g_stream ), RS_HIP_E_RUNTIME );
-  auto dec = []( unsigned u ) { unsigned b = ( u & 0x80000000u ) ? ( u ^ 0x80000000u ) : ~u; float f; std::memcpy( &f, &b, 4 ); return f; };
   float mn[3], ext = 0.0f;
   for( int a = 0; a < 3; ++a )
   {
-    mn[a] = dec( got[a] ); const float hi = dec( got[3 + a] );
+    mn[a] = bp_bounds_decode( got[a] ); const float hi = bp_bounds_decode( got[3 + a] );
     if( !( hi >= mn[a] ) || !std::isfinite( mn[a] ) || !std::isfinite( hi ) ) mn[a] = 0.0f;
     else if( hi - mn[a] > ext ) ext = hi - mn[a];
   }

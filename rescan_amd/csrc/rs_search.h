@@ -5,7 +5,7 @@
 //
 // One primitive underlies all three consumers of the reference's
 // msh_hash_grid_radius_search (lib/msh/msh_hash_grid.h:1090-1259): a WAVE owns a tile of up to
-// 64 spatially adjacent query points (Hilbert order, rs_api.hip) and searches the grid cells
+// 64 spatially adjacent query points (Hilbert order, rs_build.hip) and searches the grid cells
 // around the tile's bounding box in EXPANDING SHELLS:
 //
 //   the tile's own cells first, then the box grown by one cell, two, four, ... up to the box grown
@@ -264,7 +264,7 @@ __device__ __forceinline__ bool box_same( const CellBox& a, const CellBox& b )
 { return a.x0 == b.x0 && a.x1 == b.x1 && a.y0 == b.y0 && a.y1 == b.y1 && a.z0 == b.z0 && a.z1 == b.z1; }
 
 // Cells of one axis that can hold a point within `r` of the interval [lo,hi].  Binning of
-// the stored points (host, rs_api.hip: cell_of) and this range use the same float
+// the stored points (rs_buildplan.h: cell_of_dev) and this range use the same float
 // expression; the 0.01-cell margin is far above the rounding error of either, so the range
 // is a superset.
 __device__ __forceinline__ void axis_range( float lo, float hi, float r, float gmin, float inv_cell, int dim,

@@ -1,4 +1,4 @@
-"""The index build of a cloud (rescan_amd/csrc/rs_api.hip: cloud_create_impl, rs_build.hip, rs_buildplan.h) restated in numpy: float32
+"""The index build of a cloud (rescan_amd/csrc/rs_cloud_api.hip: cloud_create_impl, rs_build.hip, rs_buildplan.h) restated in numpy: float32
 where the code uses float, float64 where it uses double, one step per function in the build's own order.  plan() returns what
 capi.Cloud.layout() returns, to be compared for equality of integers and bits.
 

@@ -1,4 +1,4 @@
-"""Seeded clouds on which the index build (rescan_amd/csrc/rs_buildplan.h, rs_build.hip, cloud_create_impl) is easy to get wrong without
+"""Seeded clouds on which the index build (rescan_amd/csrc/rs_buildplan.h, rs_build.hip, rs_cloud_api.hip: cloud_create_impl) is easy to get wrong without
 any search noticing, in the style of tests/hard_clouds.py, whose families are reused as they are.
 
 A family is a dict: name, points (n, 3) float32, normals (n, 3) float32 or None, cells: the cell sizes it is built with (LAYOUTS unless

@@ -1,6 +1,7 @@
 // Stand-alone run of rescan_amd/csrc/rs_buildplan.h, the arithmetic of a cloud's index build, on one cloud of tests/hard_builds.py:
-// the host's decisions in cloud_create_impl's order (rs_api.hip) with every kernel's indexing expression applied to every point on
-// tables of exactly the size the library allocates — the bit table of every trial grid, the offset table, the 30-bit Hilbert key.
+// the library's own decisions (CloudPlan and its functions, as cloud_create_impl and many_build_group of rs_cloud_api.hip drive them)
+// with every kernel's indexing expression applied to every point, in the launches' place, on tables of exactly the size the library
+// allocates — the bit table of every trial grid, the offset table, the 30-bit Hilbert key.
 // Every index must be inside its table; the plan is printed (floats as their bits) and the per-point arrays are written to a file,
 // for tests/test_hard_build_cpu.py to compare with tests/build_restate.py field for field.  Built with
 // -fsanitize=address,undefined,float-cast-overflow: a conversion of a value outside its integer type ends the run.
@@ -19,6 +20,8 @@ using namespace rs;
 #define REQUIRE( c, ... ) do { if( !( c ) ) { fprintf( stderr, "buildplan_check: %s:%d: %s failed: ", __FILE__, __LINE__, #c ); fprintf( stderr, __VA_ARGS__ ); fprintf( stderr, "\n" ); exit( 1 ); } } while( 0 )
 
 static unsigned bits_of( float f ) { unsigned u; memcpy( &u, &f, 4 ); return u; }
+// the bounds kernel's order-preserving word of a float (rs_build.hip: enc)
+static unsigned enc( float f ) { const unsigned u = bits_of( f ); return ( u & 0x80000000u ) ? ~u : ( u | 0x80000000u ); }
 
 int main( int argc, char** argv )
 {
@@ -31,70 +34,59 @@ int main( int argc, char** argv )
   if( n ) REQUIRE( fread( pos.data(), 4, pos.size(), in ) == pos.size(), "points" );
   fclose( in );
 
-  // bounds: what k_build_bounds leaves (each lane's chain, their minimum) and the host's sanitising
-  float mn[3] = { 0, 0, 0 }, mx[3] = { 0, 0, 0 };
+  CloudPlan P;
+  const float *mn = P.mn, *mx = P.mx; const int* dims = P.dims;
+
+  // bounds: what k_build_bounds leaves (each lane's chain, their minimum), as its eight words, and the host's decoding and sanitising
   if( n > 0 )
   {
     float lo[3] = { FLT_MAX, FLT_MAX, FLT_MAX }, hi[3] = { -FLT_MAX, -FLT_MAX, -FLT_MAX };
     for( int i = 0; i < n; ++i ) for( int a = 0; a < 3; ++a ) bp_bounds_take( pos[3 * (size_t)i + a], lo[a], hi[a] );
-    for( int a = 0; a < 3; ++a ) { mn[a] = lo[a]; mx[a] = hi[a]; }
-    bp_sanitise_bounds( mn, mx );
+    unsigned got[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    for( int a = 0; a < 3; ++a ) { got[a] = enc( lo[a] ); got[3 + a] = enc( hi[a] ); }
+    bp_plan_bounds( P, got, n, false );
   }
   for( int a = 0; a < 3; ++a ) REQUIRE( bp_finite( mn[a] ) && bp_finite( mx[a] ) && mx[a] >= mn[a], "axis %d", a );
   printf( "mn %08x %08x %08x\nmx %08x %08x %08x\n", bits_of( mn[0] ), bits_of( mn[1] ), bits_of( mn[2] ), bits_of( mx[0] ), bits_of( mx[1] ), bits_of( mx[2] ) );
 
-  if( cell_size < 0.0f )
+  const bool asked_auto = cell_size < 0.0f;
+  bp_plan_cell_begin( P, cell_size, n );
+  for( int attempt = 0; P.undecided; ++attempt )
   {
-    cell_size = 0.1f;
-    if( n > 0 )
+    const bool last = attempt == RS_BP_TRIAL_ATTEMPTS - 1;
+    TrialGrid tg;
+    if( !bp_plan_trial( P, last, tg ) ) continue;
+    const float c0 = P.c0;                             // (of the grid to count)
+    const size_t words = tg.words();
+    std::vector<uint32_t> table( words );              // exactly what the library allocates and clears
+    REQUIRE( (double)tg.td[0] * (double)tg.td[1] * (double)tg.td[2] == tg.cells, "td" );
+    for( int a = 0; a < 3; ++a ) REQUIRE( tg.top[a] >= 0.0f && (double)tg.top[a] <= (double)( tg.td[a] - 1 ), "top of axis %d", a );
+    unsigned long long sum = 0;
+    for( int i = 0; i < n; ++i )
     {
-      float c0 = bp_trial_first_cell( mn, mx );
-      for( int attempt = 0; attempt < RS_BP_TRIAL_ATTEMPTS; ++attempt, c0 *= 2.0f )
-      {
-        const TrialGrid tg = bp_trial_grid( mn, mx, c0 );
-        if( !tg.countable() && attempt < RS_BP_TRIAL_ATTEMPTS - 1 ) continue;
-        float per_cell = RS_BP_PER_CELL_WANTED;
-        if( tg.countable() )
-        {
-          const size_t words = tg.words();
-          std::vector<uint32_t> table( words );              // exactly what the library allocates and clears
-          REQUIRE( (double)tg.td[0] * (double)tg.td[1] * (double)tg.td[2] == tg.cells, "td" );
-          for( int a = 0; a < 3; ++a ) REQUIRE( tg.top[a] >= 0.0f && (double)tg.top[a] <= (double)( tg.td[a] - 1 ), "top of axis %d", a );
-          unsigned long long sum = 0;
-          for( int i = 0; i < n; ++i )
-          {
-            const unsigned long long id = bp_trial_cell( pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], mn[0], mn[1], mn[2], tg.inv,
-                                                         tg.top[0], tg.top[1], tg.top[2], tg.td[1], tg.td[2] );
-            REQUIRE( (double)id < tg.cells && ( id >> 5 ) < words, "point %d: trial cell %llu of %.0f, word %llu of %zu", i, id, tg.cells, id >> 5, words );
-            table[id >> 5] |= 1u << ( id & 31 );
-            sum += id;
-          }
-          int occ = 0;
-          for( size_t w = 0; w < words; ++w ) occ += __builtin_popcount( table[w] );
-          printf( "trial %d c0 %08x td %llu %llu %llu top %08x %08x %08x words %zu occupied %d idsum %llu\n", attempt, bits_of( c0 ), tg.td[0], tg.td[1], tg.td[2],
-                  bits_of( tg.top[0] ), bits_of( tg.top[1] ), bits_of( tg.top[2] ), words, occ, sum );
-          per_cell = bp_per_cell( n, occ );
-        }
-        if( per_cell >= RS_BP_PER_CELL_WANTED || attempt == RS_BP_TRIAL_ATTEMPTS - 1 ) { cell_size = bp_auto_cell_of( per_cell, c0 ); break; }
-      }
-      cell_size = bp_auto_cell_scaled( cell_size, scale );
+      const unsigned long long id = bp_trial_cell( pos[3 * (size_t)i], pos[3 * (size_t)i + 1], pos[3 * (size_t)i + 2], mn[0], mn[1], mn[2], tg.inv,
+                                                   tg.top[0], tg.top[1], tg.top[2], tg.td[1], tg.td[2] );
+      REQUIRE( (double)id < tg.cells && ( id >> 5 ) < words, "point %d: trial cell %llu of %.0f, word %llu of %zu", i, id, tg.cells, id >> 5, words );
+      table[id >> 5] |= 1u << ( id & 31 );
+      sum += id;
     }
+    int occ = 0;
+    for( size_t w = 0; w < words; ++w ) occ += __builtin_popcount( table[w] );
+    printf( "trial %d c0 %08x td %llu %llu %llu top %08x %08x %08x words %zu occupied %d idsum %llu\n", attempt, bits_of( c0 ), tg.td[0], tg.td[1], tg.td[2],
+            bits_of( tg.top[0] ), bits_of( tg.top[1] ), bits_of( tg.top[2] ), words, occ, sum );
+    bp_plan_trial_counted( P, n, occ, last );
   }
-  printf( "cell_size %08x\n", bits_of( cell_size ) );
+  bp_plan_table( P, n, asked_auto, scale );
+  const float inv_cell = P.inv_cell, cell = P.cell;
+  printf( "cell_size %08x\n", bits_of( P.chosen ) );       // (as it went into the table; the table's own cell is on the next line)
 
-  int dims[3] = { 1, 1, 1 };
-  float inv_cell = 0.0f, cell = cell_size;
-  if( cell_size > 0.0f && n > 0 )
-  {
-    if( bp_table_dims( mn, mx, cell, dims ) ) inv_cell = 1.0f / cell;
-    else cell_size = cell = 0.0f;
-  }
   // the maximum's own cell is inside the table without the clamp: a query there starts its range at that cell
   if( inv_cell > 0.0f ) for( int a = 0; a < 3; ++a ) REQUIRE( floorf( ( mx[a] - mn[a] ) * inv_cell ) <= (float)( dims[a] - 1 ), "axis %d: the maximum's cell", a );
   for( int a = 0; a < 3; ++a ) REQUIRE( dims[a] >= 1 && dims[a] <= (int)RS_BP_TABLE_DIM_MAX && (int)(float)( dims[a] - 1 ) == dims[a] - 1, "dims[%d] = %d", a, dims[a] );
   const double cells_d = (double)dims[0] * dims[1] * dims[2];
   REQUIRE( cells_d <= RS_BP_TABLE_CELLS_MAX, "%.0f cells", cells_d );
   const size_t n_cells = (size_t)dims[0] * dims[1] * dims[2];
+  REQUIRE( n_cells == P.n_cells, "n_cells %zu, the plan's %zu", n_cells, P.n_cells );
   printf( "cell %08x inv_cell %08x dims %d %d %d\n", bits_of( inv_cell > 0.0f ? cell : 0.0f ), bits_of( inv_cell ), dims[0], dims[1], dims[2] );
 
   std::vector<uint32_t> counts( n_cells + 1 ), ids( (size_t)n ), keys( (size_t)n );
@@ -109,12 +101,10 @@ int main( int argc, char** argv )
     if( !counts[id]++ ) ++occupied;
     ids[i] = id;
   }
-  const float lim_cell = cell_size > 0.0f ? cell : 0.1f;
-  if( !( cell_size > 0.0f ) ) occupied = bp_brute_occupied( n, mn, mx );
-  const float limit = query_extent_limit( n, occupied, lim_cell, extent_max );
-  printf( "occupied %zu limit %08x\n", occupied, bits_of( limit ) );
+  bp_plan_query_layout( P, n, occupied, extent_max );
+  printf( "occupied %zu limit %08x\n", P.occupied, bits_of( P.extent_limit ) );
 
-  const float hs = bp_hilbert_scale( mn, mx );
+  const float hs = P.hscale;
   for( int i = 0; i < n; ++i )
   {
     uint32_t c[3];

@@ -145,7 +145,7 @@ def axis_cells(lo, hi, r, gmin, cell, dim):
 
 
 def grid_of(c):
-    """(min corner, dims) as the library lays the target's grid out: rs_api.hip"""
+    """(min corner, dims) as the library lays the target's grid out: rs_buildplan.h (bp_table_dims)"""
     mn, mx = c["tgt"].min(0), c["tgt"].max(0)
     dims = [int(np.floor((float(mx[a]) - float(mn[a])) / float(c["cell"]))) + 1 for a in range(3)]
     return mn, dims

@@ -5,8 +5,9 @@ tests/isect_restate.py, tests/resample_restate.py, rs_hip_shuffle_plan, numpy, t
 extensions, against the same call made first after rs_hip_arrange_release.
 Each test runs in one child process under its own time limit, so that the thread's workspaces start empty whatever ran before;
 nothing here provokes a fault or a HIP error: every refusal is one of arguments.
-The second half does the same for the four host units of the C ABI proper (rs_api.hip, rs_icp_api.hip, rs_score.hip,
-rs_rows_api.hip: DevBuf, ProfScope), each with a workspace of its own: calls of different units alternate while their buffers grow,
+The second half does the same for the host units of the C ABI proper: of the five, rs_api.hip holds the runtime state and the other
+four (rs_cloud_api.hip, rs_icp_api.hip, rs_score.hip, rs_rows_api.hip: DevBuf, ProfScope) a workspace each: calls of different units
+alternate while their buffers grow,
 against the committed fixtures with the parity suite's own comparisons (tests/test_gpu_parity.py)."""
 import subprocess
 import sys
@@ -261,7 +262,7 @@ print("ok")
 """)
 
 
-# ---- the four host units of the C ABI: every step IS a case of tests/test_gpu_parity.py, called on its fixture ----
+# ---- the host units of the C ABI with a workspace (clouds, ICP, scores, rows): every step IS a case of tests/test_gpu_parity.py, called on its fixture ----
 API_PRELUDE = r"""
 import ctypes as C, os, sys
 import numpy as np
