@@ -146,6 +146,14 @@ int64_t rsd_compute_neighborhood( const rsd_vec3_t* pos, const rsd_vec3_t* nor, 
  * points within voxel_size, where a reference search would be truncated). */
 int32_t rsd_level_poisson( const rsd_vec3_t* pos, int32_t n, float voxel_size, int32_t level, int32_t* sample_idx );
 
+/* The levels first_level .. first_level + n_levels - 1 of one cloud in one call — the loop of rs_pointcloud_compute_levels
+ * (lib/rs/rs_pointcloud.h:1311-1315), every level sampled from pc->positions[0] as the reference does.  voxel_size is indexed by the
+ * level NUMBER (pass pc->voxel_size); the caps are derived from the level numbers as rsd_level_poisson derives its own.
+ * sample_idx[k] (capacity n) and counts[k] receive what rsd_level_poisson( pos, n, voxel_size[first_level + k], first_level + k, . )
+ * returns.  At most 8 levels.  Returns 0 (< 0: error, nothing written; RS_HIP_E_CAPACITY as above, for any of the levels). */
+int32_t rsd_levels_poisson( const rsd_vec3_t* pos, int32_t n, const float* voxel_size, int32_t first_level, int32_t n_levels,
+                            int32_t* const* sample_idx, int32_t* counts );
+
 /* rs_pointcloud_uniform_resample (lib/rs/rs_pointcloud.h:1132-1227) on in_mesh's level 0 and faces_ind: the level-0 arrays of
  * out_pc, bit for bit (qualities stay unset, as in the reference).  Returns the sample count — what the caller passes to
  * rs_pointcloud__allocate_level — or a negative RS_HIP_E_* code with nothing written.  A call with every output NULL returns the

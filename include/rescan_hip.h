@@ -442,6 +442,35 @@ int rs_hip_level_samples( const rs_hip_cloud_t* cloud, float radius, int32_t max
 rs_hip_cloud_t* rs_hip_cloud_create_level( const rs_hip_cloud_t* base, float radius, int32_t max_n_neigh, float cell_size,
                                            int32_t* sample_idx, int32_t* n_samples );
 
+/* Levels of many clouds in one call. Problem (c, l) = level l of bases[c]: the samples rs_hip_level_samples( bases[c], radii[l],
+ * max_n_neigh[l] ) returns, and out[c * n_levels + l] the cloud rs_hip_cloud_create_level( bases[c], radii[l], max_n_neigh[l],
+ * cell_sizes ? cell_sizes[l] : -1 ) makes of them, to the byte (layouts, host copies, reported sizes).  The reference samples every
+ * level from level 0 (rs_pointcloud.h:989-1011, :1305-1315), so the problems are independent and are decided side by side: one
+ * neighbourhood sweep per base at the largest radius, one frontier launch per step for all problems, one batched index build; the
+ * launches and read-backs of a call do not grow with n_clouds or n_levels.
+ *   All or nothing: RS_HIP_OK, or an error code with out / sample_idx / n_samples untouched and nothing left allocated.
+ *   Over-cap: if any point of any problem has more than that level's max_n_neigh points within that level's radius the whole call
+ *   fails with RS_HIP_E_CAPACITY; the text names the lowest (cloud index, level index) that is over.  Decided after the counting
+ *   pass, before anything is written through the counts.
+ *   Accepted: an empty base (each of its levels is an empty cloud), the same base listed more than once, bases with and without
+ *   normals in one batch (a level has normals iff its base has), n_clouds == 0 or n_levels == 0 (RS_HIP_OK, nothing done), radii in
+ *   any order, equal radii with different caps.
+ *   RS_HIP_E_ARG, before any launch: a NULL base, a radius that is not > 0, a cap <= 0, n_levels > 8, n_clouds * n_levels > 32768.
+ *   RS_HIP_E_CAPACITY, before any launch: the bases decided together have more than 2^30 = 1 073 741 824 (points x n_levels) in sum
+ *   — a frontier item is (global id << 1) | flag in an int.  (A base of more than 1 000 000 points is not decided with the others
+ *   but by rs_hip_level_samples' own path inside the call, and does not count.)
+ *   The clouds of a call share device allocations, freed with the last of them; each is destroyed by rs_hip_cloud_destroy.  The
+ *   bases may be destroyed right after the call. */
+int rs_hip_level_samples_many( const rs_hip_cloud_t* const* bases, int32_t n_clouds,
+                               const float* radii, const int32_t* max_n_neigh, int32_t n_levels,
+                               int32_t* const* sample_idx,   /* [c * n_levels + l], capacity size of bases[c]; an entry may be NULL */
+                               int32_t* n_samples,           /* n_clouds * n_levels */
+                               int32_t* n_rounds );          /* may be NULL: frontier steps the batch needed */
+int rs_hip_cloud_create_levels_many( const rs_hip_cloud_t* const* bases, int32_t n_clouds,
+                                     const float* radii, const int32_t* max_n_neigh, const float* cell_sizes /* may be NULL */, int32_t n_levels,
+                                     rs_hip_cloud_t** out,   /* n_clouds * n_levels */
+                                     int32_t* const* sample_idx /* may be NULL as a whole or per entry */, int32_t* n_samples /* may be NULL */ );
+
 /* The gathers that end the level builder (lib/rs/rs_pointcloud.h:1090-1099): for each of n_arrays per-point arrays of the
  * base level (host pointers, `words[a]` 32-bit words per point: 3 for positions / normals / colours, 1 for radii, qualities,
  * class and instance ids), dst[a][i] = src[a][sample_idx[i]].  Entries with a NULL src or dst are skipped. */

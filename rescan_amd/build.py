@@ -7,8 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librescan_hip.so")
 DROPIN = os.path.join(HERE, "librescan_dropin.so")
-SOURCES = ["rs_icp_search.hip", "rs_icp_update.hip", "rs_icp_faithful.hip", "rs_icp_chain.hip", "rs_score.hip", "rs_rows.hip", "rs_build.hip", "rs_knn.hip", "rs_isect.hip", "rs_arrange.hip", "rs_mesh.hip", "rs_fuse.hip", "rs_planes.hip", "rs_split.hip", "rs_propose.hip", "rs_api.hip", "rs_cloud_api.hip", "rs_icp_api.hip", "rs_rows_api.hip"]
-HEADERS = ["rs_device.h", "rs_api.h", "rs_host.h", "rs_math.h", "rs_buildplan.h", "rs_switches.h", "rs_search.h", "rs_rowtable.h", "rs_xcdmap.h", "rs_icp.h", "rs_icp_estimate.h", "rs_tail_dbg.h", "rs_voxel.h", "rs_mesh.h", "rs_fuse.h", "rs_planes.h", "rs_split.h", "rs_propose.h", "rs_dropin.cpp", os.path.join("..", "..", "include", "rescan_hip.h"),
+SOURCES = ["rs_icp_search.hip", "rs_icp_update.hip", "rs_icp_faithful.hip", "rs_icp_chain.hip", "rs_score.hip", "rs_rows.hip", "rs_build.hip", "rs_knn.hip", "rs_isect.hip", "rs_arrange.hip", "rs_mesh.hip", "rs_fuse.hip", "rs_planes.hip", "rs_split.hip", "rs_propose.hip", "rs_levels.hip", "rs_api.hip", "rs_cloud_api.hip", "rs_icp_api.hip", "rs_rows_api.hip"]
+HEADERS = ["rs_device.h", "rs_api.h", "rs_host.h", "rs_math.h", "rs_buildplan.h", "rs_switches.h", "rs_search.h", "rs_rowtable.h", "rs_xcdmap.h", "rs_icp.h", "rs_icp_estimate.h", "rs_tail_dbg.h", "rs_voxel.h", "rs_mesh.h", "rs_fuse.h", "rs_planes.h", "rs_split.h", "rs_propose.h", "rs_levels.h", "rs_dropin.cpp", os.path.join("..", "..", "include", "rescan_hip.h"),
            os.path.join("..", "..", "include", "rescan_dropin.h")]
 # -ffp-contract=off: the neighbour-deciding arithmetic must round exactly like the reference's
 # scalar SSE2 code (no FMA); see DESIGN.md.

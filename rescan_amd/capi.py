@@ -115,6 +115,8 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "rs_hip_cloud_create_level": (C.c_void_p, [C.c_void_p, C.c_float, C.c_int32, C.c_float, i32p, C.POINTER(C.c_int32)]),
     "rs_hip_level_samples": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, i32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rs_hip_level_samples_many": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "rs_hip_cloud_create_levels_many": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rs_hip_cloud_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "rs_hip_resample_plan": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "rs_hip_uniform_resample": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64] + [C.c_void_p] * 7),
@@ -338,6 +340,34 @@ class Cloud:
         self._pos = base._pos[idx]
         self._nor = None if base._nor is None else base._nor[idx]
         return self, idx
+
+    @classmethod
+    def levels_many(cls, bases, levels, cell_size=-1.0):
+        """Every level of `levels` = [(radius, max_n_neigh), ...] of every base in one call (rs_hip_cloud_create_levels_many): each
+        is, to the byte, what level_of(base, radius, max_n_neigh, cell_size) makes.  cell_size: one value for all, or one per level.
+        Returns [[(cloud, sample indices), ...per level], ...per base]; all or nothing."""
+        lib = load()
+        nc, nl, radii, caps, handles, idx, ptrs = _levels_many_args(bases, levels)
+        cells = np.full(nl, cell_size, np.float32) if np.ndim(cell_size) == 0 else np.ascontiguousarray(cell_size, np.float32).ravel()
+        if len(cells) != nl:
+            raise ValueError("one cell size per level")
+        made = (C.c_void_p * max(1, nc * nl))()
+        counts = np.zeros(max(1, nc * nl), np.int32)
+        _check(lib.rs_hip_cloud_create_levels_many(C.addressof(handles), nc, radii.ctypes.data, caps.ctypes.data, cells.ctypes.data, nl,
+                                                   C.addressof(made), C.addressof(ptrs), counts.ctypes.data))
+        out = []
+        for c, base in enumerate(bases):
+            row = []
+            for l in range(nl):
+                p = c * nl + l
+                self = cls.__new__(cls)
+                ind = idx[p][:counts[p]].copy()
+                self.handle = made[p]; self.n = int(counts[p])
+                self._pos = base._pos[ind]
+                self._nor = None if base._nor is None else base._nor[ind]
+                row.append((self, ind))
+            out.append(row)
+        return out
 
     @classmethod
     def resampled(cls, pos, nor, faces, cell_size=-1.0):
@@ -1311,6 +1341,26 @@ def level_samples(cloud, radius, max_n_neigh):
     n = C.c_int32(); r = C.c_int32()
     _check(load().rs_hip_level_samples(cloud.handle, float(radius), int(max_n_neigh), out, C.byref(n), C.byref(r)))
     return out[:n.value].copy(), r.value
+
+
+def _levels_many_args(bases, levels):
+    nc, nl = len(bases), len(levels)
+    radii = np.array([r for r, _ in levels], np.float32)
+    caps = np.array([k for _, k in levels], np.int32)
+    handles = (C.c_void_p * max(1, nc))(*[b.handle for b in bases])
+    idx = [np.zeros(max(b.n, 1), np.int32) for b in bases for _ in range(nl)]
+    ptrs = (C.c_void_p * max(1, nc * nl))(*[a.ctypes.data for a in idx])
+    return nc, nl, radii, caps, handles, idx, ptrs
+
+
+def level_samples_many(bases, levels):
+    """rs_hip_level_samples for every level of `levels` = [(radius, max_n_neigh), ...] of every base, decided in one call
+    (rs_hip_level_samples_many): ([[sample indices, ...per level], ...per base], rounds)."""
+    nc, nl, radii, caps, handles, idx, ptrs = _levels_many_args(bases, levels)
+    counts = np.zeros(max(1, nc * nl), np.int32); r = C.c_int32()
+    _check(load().rs_hip_level_samples_many(C.addressof(handles), nc, radii.ctypes.data, caps.ctypes.data, nl, C.addressof(ptrs), counts.ctypes.data,
+                                            C.byref(r)))
+    return [[idx[c * nl + l][:counts[c * nl + l]].copy() for l in range(nl)] for c in range(nc)], r.value
 
 
 def sincosf_model(x):

@@ -662,6 +662,15 @@ int api_clouds_from_device( const float* pos, const float* nor, const int64_t* f
     in[(size_t)k] = ManyInput{ pos + 3 * (size_t)first[k], nor ? nor + 3 * (size_t)first[k] : nullptr, (int32_t)count[k], cell_size };
   return cloud_create_many_impl( in.data(), n_segments, true, out );
 }
+int api_clouds_from_device_each( const float* pos, const float* nor, const int64_t* first, const int64_t* count, const int32_t* has_nor, const float* cell_sizes,
+                                 int32_t n_segments, rs_hip_cloud** out )
+{
+  std::vector<ManyInput> in( (size_t)std::max( 0, n_segments ) );
+  for( int32_t k = 0; k < n_segments; ++k )
+    in[(size_t)k] = ManyInput{ pos + 3 * (size_t)first[k], has_nor[k] ? nor + 3 * (size_t)first[k] : nullptr, (int32_t)count[k], cell_sizes[k] };
+  return cloud_create_many_impl( in.data(), n_segments, true, out );
+}
+const QueryView* api_cloud_query( const rs_hip_cloud* c ) { return c ? &c->qview : nullptr; }
 CloudPoints api_cloud_points( const rs_hip_cloud* c )
 {
   return CloudPoints{ c->d_qpos, c->has_nor ? c->d_qnor : nullptr, c->d_qby_orig, c->n };

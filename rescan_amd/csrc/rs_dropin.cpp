@@ -887,6 +887,26 @@ int32_t rsd_level_poisson( const rsd_vec3_t* pos, int32_t n, float voxel_size, i
   return n_samples;
 }
 
+int32_t rsd_levels_poisson( const rsd_vec3_t* pos, int32_t n, const float* voxel_size, int32_t first_level, int32_t n_levels,
+                            int32_t* const* sample_idx, int32_t* counts )
+{
+  if( n_levels < 0 || n_levels > 8 || first_level < 0 || ( n_levels > 0 && ( !voxel_size || !sample_idx || !counts ) ) ) return RS_HIP_E_ARG;
+  const CloudRef c = cached_cloud( pos, nullptr, n, -1.0f );
+  if( !c ) return RS_HIP_E_RUNTIME;
+  float radii[8]; int32_t caps[8];
+  for( int32_t k = 0; k < n_levels; ++k )
+  {
+    const int32_t level = first_level + k;
+    size_t max_n_neigh = (size_t)( 1024 * ( ( level ) / (float)( 5 - 1 ) ) );      // rs_pointcloud.h:995 (RSPC_N_LEVELS = 5)
+    if( !max_n_neigh ) max_n_neigh = 256;                                           // :996
+    radii[k] = voxel_size[level]; caps[k] = (int32_t)max_n_neigh;
+  }
+  const rs_hip_cloud_t* base = c.get();
+  int rc = rs_hip_level_samples_many( &base, 1, radii, caps, n_levels, sample_idx, counts, nullptr );
+  if( rc ) { complain( "levels_poisson" ); return rc; }
+  return RS_HIP_OK;
+}
+
 int64_t rsd_uniform_resample( const rsd_vec3_t* pos, const rsd_vec3_t* nor, const rsd_vec3_t* col, const float* radii,
                               const int32_t* class_ids, const int32_t* instance_ids, int64_t n_vertices,
                               const int32_t* faces_ind, int64_t n_faces, int64_t capacity,

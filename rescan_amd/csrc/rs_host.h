@@ -1,5 +1,5 @@
 // Host runtime shared by the translation units with entry points of their own (rs_knn.hip, rs_isect.hip, rs_arrange.hip,
-// rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip): what they need from the host side of the C ABI, a growable buffer, the failure
+// rs_mesh.hip, rs_fuse.hip, rs_planes.hip, rs_propose.hip, rs_levels.hip): what they need from the host side of the C ABI, a growable buffer, the failure
 // path, a profiling span and the grid size of a launch.  Host only: no kernel file needs it.  The api_* functions are defined by the unit
 // that owns what they reach: api_level_workspace / api_cloud_from_level_workspace in rs_rows_api.hip, api_score_poses_device in
 // rs_score.hip, api_cloud_* / api_clouds_from_device in rs_cloud_api.hip, the others in rs_api.hip.
@@ -27,6 +27,13 @@ struct ::rs_hip_cloud* api_cloud_from_level_workspace( bool with_nor, int32_t n,
 // untouched.  Synchronises the stream.
 int             api_clouds_from_device( const float* pos, const float* nor, const int64_t* first, const int64_t* count, int32_t n_segments, float cell_size,
                                         struct ::rs_hip_cloud** out );
+// the same with a normals flag and a cell size per segment (rs_levels.hip: levels of bases with and without normals, each level with
+// its own cell): segment k has normals iff has_nor[k], read at nor + 3 * first[k]; an empty segment with the flag set is an empty
+// cloud with normals
+int             api_clouds_from_device_each( const float* pos, const float* nor, const int64_t* first, const int64_t* count, const int32_t* has_nor,
+                                             const float* cell_sizes, int32_t n_segments, struct ::rs_hip_cloud** out );
+// a cloud as a query set (Hilbert order, tiles) for a sweep in another unit (rs_levels.hip)
+const QueryView* api_cloud_query( const struct ::rs_hip_cloud* c );
 // a cloud's points for a reader in another unit (rs_fuse.hip): the query layout (Hilbert order, 16-byte records) and the map from an
 // original index to its slot there; nor is null for a cloud without normals
 struct CloudPoints { const float4* qpos; const float4* qnor; const int* by_orig; int n; };
